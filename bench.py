@@ -12,7 +12,9 @@ a ring of distinct pileups whose total size exceeds the 256 MiB Infinity Cache, 
 Loci shard by interval across ranks (weak scaling: every rank owns its own 100k-locus shard per step); the only
 collective is one RCCL all-reduce of the int64[4] per-chromosome summary at the end of the timed region.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` and `cpu_baseline` objects.
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run sets up, warms up, times the K steps and prints the
+headline; `--full` adds every other figure (`roofline`, `pipelined`, `shard_check`, the end-to-end and config samples, `cpu_baseline`, ...).
+`--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy (see dump_outputs).
 """
 import argparse
 import json
@@ -40,11 +42,37 @@ TIME_EVERY = 1          # the second pass (below) puts dispatch-bound HIP events
                         # reports for the same command.  The timed region itself carries no per-launch events (they cost 5-10 us of every
                         # step: rounds 1-2 quoted `value` with them in) — one HIP event in front of it and one behind it on the launch stream
 PIPELINE_STREAMS = 3    # the extra 'pipelined' figure: pisces_hip_call_tiles_batched spreads the steps over its 3 lanes
+DUMP_LIMIT_BYTES = 64 << 20
 
 
 def algorithmic_bytes(n_obs, n_loci, n_records):
     """4 B per observation tuple + 1 reference byte per locus + 64 B per called-allele record."""
     return 4 * n_obs + n_loci + 64 * n_records
+
+
+def dump_outputs(path, records, tile_results):
+    """--dump-outputs: what a caller of pisces_hip_call_tiles receives from one step — its called alleles in (position, ref, alt) order,
+    one array per record field (`allele_<field>.npy`), and every tile's counts (`tile_<field>.npy`) — as float64, which holds every
+    int32 field exactly.  Above DUMP_LIMIT_BYTES a fixed seeded sample of the alleles is written, with their rows in `allele_row.npy`.
+    Returns the bytes written."""
+    import numpy as np
+    from pisces_amd import _abi
+    alleles = _abi.records_in_order(records, tile_results)
+    arrays = {f"tile_{f}": tile_results[f] for f in ("n_records", "n_candidate_loci", "n_called")}
+    room = DUMP_LIMIT_BYTES - 8 * sum(a.size for a in arrays.values())
+    row_bytes = 8 * sum(int(np.prod(alleles.dtype[f].shape)) for f in alleles.dtype.names)
+    if len(alleles) * row_bytes > room:
+        rows = np.sort(np.random.default_rng(0).choice(len(alleles), room // (row_bytes + 8), replace=False))
+        alleles = alleles[rows]
+        arrays["allele_row"] = rows
+    arrays.update({f"allele_{f}": alleles[f] for f in alleles.dtype.names})
+    os.makedirs(path, exist_ok=True)
+    written = 0
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        np.save(os.path.join(path, name + ".npy"), a)
+        written += a.nbytes
+    return written
 
 
 def host_cpu():
@@ -1032,6 +1060,11 @@ def main():
     ap.add_argument("--warmup", type=int, default=12)
     ap.add_argument("--loci", type=int, default=N_LOCI)
     ap.add_argument("--depth", type=int, default=DEPTH)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, every other figure: the per-kernel roofline, the pipelined figure, the shard check, the C-ABI "
+                         "reduce and config 4 (N > 1), the end-to-end and config samples, the CPU baselines (the --no-* options trim it)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed (called alleles in order, per-tile counts) as DIR/<name>.npy, float64")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-end-to-end", action="store_true", help="skip the streaming-surface figures (host reads -> records)")
     ap.add_argument("--no-large-bam", action="store_true", help="skip the 265 MB BAM figure of end_to_end_full (~25 s to make the file)")
@@ -1042,6 +1075,10 @@ def main():
                     help="2 (default): the configuration the metric is quoted on; 3 / 5: BASELINE configs 3 / 5 as stated, from reads through the "
                          "streaming surface; 4: BASELINE config 4 as stated")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.config != 2:
+        ap.error("--dump-outputs writes the timed steps of config 2")
     launched = launch_ranks(args, sys.argv[1:])
     if launched is not None:
         return launched
@@ -1111,7 +1148,7 @@ def main():
     with torch.cuda.stream(stream):
         records = torch.zeros(cap * 64, dtype=torch.uint8, device=dev)
         tile_results = torch.zeros(n_tiles * _abi.TILE_RESULT_DTYPE.itemsize, dtype=torch.uint8, device=dev)
-        n_extra = 0 if args.no_pipelined else PIPELINE_STREAMS - 1
+        n_extra = PIPELINE_STREAMS - 1 if args.full and not args.no_pipelined else 0
         p_records = [records] + [torch.zeros_like(records) for _ in range(n_extra)]
         p_results = [tile_results] + [torch.zeros_like(tile_results) for _ in range(n_extra)]
     torch.cuda.synchronize(dev)
@@ -1165,29 +1202,13 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed = float(t.item())
 
-    # ---- the same K launches once more between two HIP events on the launch stream (torch.cuda.Event would see torch's only): the
-    # device-side span of the K launches back to back.  Outside the timed region: the two event records are ~8 us of its ~830. ----
-    caller.mark(0, stream)
-    for i in range(args.steps):
-        step(args.warmup + i)
-    caller.mark(1, stream)
+    # ---- the last timed step's output, read back before anything else launches (outside the timed region): sanity, --dump-outputs ----
     torch.cuda.synchronize(dev)
-    span_ms = caller.marked_ms() / args.steps
-
-    # ---- the same K launches once more, every one with the HIP events of its own dispatch (hipExtLaunchKernel start / stop): the
-    # kernel's duration as rocprofv3 reports it.  Outside the timed region: the events put 5-10 us between launches. ----
-    caller.set_timing(TIME_EVERY)
-    for i in range(args.steps):
-        step(args.warmup + i)
-    torch.cuda.synchronize(dev)
-    kernel_ms_total, launches = caller.kernel_time()
-    caller.set_timing(False)
-    caller.device_totals(reset=True)
-
-    # ---- sanity on the last step's output (outside the timed region) ----
     tr = tile_results.cpu().numpy().view(_abi.TILE_RESULT_DTYPE)
     assert int(tr["n_records"].sum()) * args.steps == totals["records"]
     assert int(tr["n_candidate_loci"].sum()) == my_loci, "every covered locus must be a candidate locus in gVCF mode"
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, records.cpu().numpy().view(_abi.CALLED_ALLELE_DTYPE), tr)
 
     if not use_dist:   # (one rank: the summary is this rank's totals; the tensor is made outside the timed region)
         summary = torch.tensor([totals["records"], totals["candidate_loci"], totals["called"], totals["tiles"]], dtype=torch.int64)
@@ -1195,10 +1216,30 @@ def main():
     assert sum_loci == total_loci * args.steps, (sum_loci, total_loci, args.steps)   # the shards cover the interval set exactly once
     value = sum_loci / elapsed
 
+    if args.full:
+        # ---- the same K launches once more between two HIP events on the launch stream (torch.cuda.Event would see torch's only): the
+        # device-side span of the K launches back to back.  Outside the timed region: the two event records are ~8 us of its ~830. ----
+        caller.mark(0, stream)
+        for i in range(args.steps):
+            step(args.warmup + i)
+        caller.mark(1, stream)
+        torch.cuda.synchronize(dev)
+        span_ms = caller.marked_ms() / args.steps
+
+        # ---- the same K launches once more, every one with the HIP events of its own dispatch (hipExtLaunchKernel start / stop): the
+        # kernel's duration as rocprofv3 reports it.  Outside the timed region: the events put 5-10 us between launches. ----
+        caller.set_timing(TIME_EVERY)
+        for i in range(args.steps):
+            step(args.warmup + i)
+        torch.cuda.synchronize(dev)
+        kernel_ms_total, launches = caller.kernel_time()
+        caller.set_timing(False)
+        caller.device_totals(reset=True)
+
     # ---- one cut of the partition checked on the device (outside the timed region): the two sides of this rank's cut, each called by
     # its own handle from the reads shard.reads_for_shard hands it (halo reads on both sides), concatenate to the unsharded window ----
     shard_check = None
-    if not args.no_shard_check:
+    if args.full and not args.no_shard_check:
         bs = cfg.block_size
         if world > 1:
             cut = own_lo if rank > 0 else own_hi + 1
@@ -1226,7 +1267,7 @@ def main():
     # buffers per lane).  Batches are independent, so the call phase at the end of one launch overlaps the streaming phase of the next, which a
     # single in-order stream forbids; this is how a host with several blocks in flight drives the library.
     pipelined_elapsed = None
-    if not args.no_pipelined:
+    if args.full and not args.no_pipelined:
         # pisces_hip_call_tiles_batched spreads the launches over the handle's own HIP streams ("lanes"); every batch in flight needs its
         # own output buffers
         # (allocated with the other buffers in front of the first launch: see "Stream discipline" above)
@@ -1257,7 +1298,7 @@ def main():
     # calls), outside the timed region, after every torch collective of this run, and not fatal: it runs on a side thread with a time
     # limit, so that a communicator that cannot be set up on some node costs this field and not the bench line ----
     c_abi_reduce, c_abi_hung = None, False
-    if world > 1:
+    if args.full and world > 1:
         import threading
         box = {}
 
@@ -1282,37 +1323,15 @@ def main():
     # weak-scaling `value` (which stays config 2 per GPU, so that the line's value means the same thing at every N): every rank takes its
     # shards of the 8-way cut in turn, totals reduced.  Outside the timed region; BENCH_CONFIG4=0 skips it (it takes ~2 minutes / N). ----
     config4_line = None
-    if world > 1 and os.environ.get("BENCH_CONFIG4", "1") != "0":
+    if args.full and world > 1 and os.environ.get("BENCH_CONFIG4", "1") != "0":
         try:
             config4_line = config4_job(torch, dist, world, rank, local_rank, use_dist)
         except Exception as e:   # noqa: BLE001  (an extra figure: it must not cost the bench line)
             config4_line = {"error": str(e)[:300]}
 
     if rank == 0:
-        # roofline of the dominant (only) kernel: algorithmic bytes per launch / mean kernel duration from HIP
-        # events recorded on the launch stream around every TIME_EVERY-th launch of the timed region
         n_obs = float(np.mean([p.n_obs for p in ring]))
         rec_per_launch = totals["records"] / max(args.steps, 1)
-        bytes_per_launch = algorithmic_bytes(n_obs, my_loci, rec_per_launch)
-        kernel_ms = kernel_ms_total / max(launches, 1)
-        # `achieved`: against the kernel's own duration (the events of its dispatch, second pass: what rocprofv3's kernel statistics of this
-        # command say); timed_region_ms_per_launch is the timed region's two events / K, gaps between launches included
-        achieved = bytes_per_launch / (kernel_ms * 1e-3) / 1e9
-        traffic, traffic_run = None, None
-        tpath = os.path.join(ROOT, "profiles", "traffic.json")
-        if os.path.exists(tpath):   # written from separate rocprofv3 --pmc passes of this same command
-            try:
-                tj = json.load(open(tpath))
-                from pisces_amd import build as native_build
-                if tj.get("loci") == args.loci and tj.get("depth") == args.depth:
-                    # the figure is only printed for the kernels it was collected on: the file carries the hash of the library's sources
-                    if tj.get("source_hash") == native_build.source_hash():
-                        traffic = tj.get("hbm_bytes_per_launch")
-                        traffic_run = tj.get("run")
-                    else:
-                        traffic_run = "stale: profiles/traffic.json was collected on other sources (%s); re-run tools/profile_round.sh" % tj.get("run")
-            except Exception:
-                traffic = None
         out = {
             "metric": "candidate loci/s at 500x depth",
             "value": value,
@@ -1332,62 +1351,85 @@ def main():
                        "records_per_step": rec_per_launch, "ring_batches": RING_BATCHES, "tile_loci": tile_loci, "tiles_per_step": n_tiles,
                        "interval_set": {"loci": total_loci, "intervals": len(intervals), "rank0_shard": [int(own_lo), int(own_hi)]},
                        "parallelism": f"interval-shard x{world}"},
-            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
-                         "kernel": "pisces::call_tiles_wave_kernel", "kernel_ms": kernel_ms, "launches_timed": launches,
-                         "timed_region_ms_per_launch": span_ms, "frac_timed_region": bytes_per_launch / (span_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                         "algorithmic_bytes_per_launch": bytes_per_launch,
-                         "how": "kernel_ms: the K launches of the timed region launched once more, each with the HIP events of its own dispatch "
-                                "(hipExtLaunchKernel start / stop: the duration rocprofv3 reports; those events put 5-10 us between launches, so "
-                                "the timed region carries none); timed_region_ms_per_launch: the K launches once more with one HIP event in front "
-                                "of and one behind them on the launch stream, / K (gaps between launches included)"},
         }
-        # context only (SURVEY 8d asks for the measured peak beside the spec one; frac stays against the spec peak):
-        # a plain streaming read of 1 GiB with the kernel's own load pattern
-        out["roofline"]["peak_measured_read"] = caller.probe_read_bandwidth(1 << 30, 6)
-        out["roofline"]["traffic_from"] = traffic_run   # the rocprofv3 --pmc passes of tools/profile_round.sh the figure was collected in (not this run)
-        if pipelined_elapsed is not None:
-            p_ms = pipelined_elapsed / args.steps * 1e3
-            out["pipelined"] = {"streams": PIPELINE_STREAMS, "value": total_loci * args.steps / pipelined_elapsed,
-                                "unit": "candidate loci/s", "ms_per_step": p_ms,
-                                "hbm_frac": bytes_per_launch / (p_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                                "note": "same steps over several HIP streams; not the contract's value, not a per-kernel roofline"}
-        if shard_check is not None:
-            out["shard_check"] = shard_check
-        # ranks that joined the collectives of this run: torch.distributed's process group (the timed region's reduce) and, N > 1, ncclCommCount
-        # of the communicator the library itself made through the C ABI (1 at N = 1: no communicator, the value is the 1-GPU path's)
-        out["rccl_ranks"] = {"torch_process_group": dist.get_world_size() if use_dist else 1,
-                             "c_abi_comm_count": (c_abi_reduce or {}).get("ranks", caller.comm_ranks() if world == 1 else None)}
-        if c_abi_reduce is not None:
-            out["c_abi_reduce"] = c_abi_reduce
-        if config4_line is not None:
-            out["config4_strong_scaling"] = config4_line
-        if not args.no_end_to_end and world == 1:     # the drop-in boundary's own rates, rank 0 at N=1 only
-            out["end_to_end"] = end_to_end(ring[0], cfg, engine)
-            try:
-                out["end_to_end_full"], out["roofline_streaming"] = end_to_end_full(ring[0], cfg, engine, torch)
-            except Exception as e:   # noqa: BLE001  (extra figures: they must not cost the bench line)
-                out["end_to_end_full"] = {"error": str(e)[:200]}
-            try:
-                out["roofline_chain"] = chain_roofline(ring[0], cfg, engine, torch)
-            except Exception as e:   # noqa: BLE001  (extra figures: they must not cost the bench line)
-                out["roofline_chain"] = {"error": str(e)[:200]}
-            for key, sample in (("roofline_config3", config3_sample), ("roofline_config5", config5_sample), ("roofline_config4", config4_sample)):
+        if args.full:
+            # roofline of the dominant (only) kernel: algorithmic bytes per launch / mean kernel duration from HIP
+            # events recorded on the launch stream around every TIME_EVERY-th launch of the timed region
+            bytes_per_launch = algorithmic_bytes(n_obs, my_loci, rec_per_launch)
+            kernel_ms = kernel_ms_total / max(launches, 1)
+            # `achieved`: against the kernel's own duration (the events of its dispatch, second pass: what rocprofv3's kernel statistics of this
+            # command say); timed_region_ms_per_launch is the timed region's two events / K, gaps between launches included
+            achieved = bytes_per_launch / (kernel_ms * 1e-3) / 1e9
+            traffic, traffic_run = None, None
+            tpath = os.path.join(ROOT, "profiles", "traffic.json")
+            if os.path.exists(tpath):   # written from separate rocprofv3 --pmc passes of this same command
                 try:
-                    out[key] = sample(engine, torch)
+                    tj = json.load(open(tpath))
+                    from pisces_amd import build as native_build
+                    if tj.get("loci") == args.loci and tj.get("depth") == args.depth:
+                        # the figure is only printed for the kernels it was collected on: the file carries the hash of the library's sources
+                        if tj.get("source_hash") == native_build.source_hash():
+                            traffic = tj.get("hbm_bytes_per_launch")
+                            traffic_run = tj.get("run")
+                        else:
+                            traffic_run = "stale: profiles/traffic.json was collected on other sources (%s); re-run tools/profile_round.sh" % tj.get("run")
+                except Exception:
+                    traffic = None
+            out["roofline"] = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                               "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
+                               "kernel": "pisces::call_tiles_wave_kernel", "kernel_ms": kernel_ms, "launches_timed": launches,
+                               "timed_region_ms_per_launch": span_ms, "frac_timed_region": bytes_per_launch / (span_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                               "algorithmic_bytes_per_launch": bytes_per_launch,
+                               "how": "kernel_ms: the K launches of the timed region launched once more, each with the HIP events of its own dispatch "
+                                      "(hipExtLaunchKernel start / stop: the duration rocprofv3 reports; those events put 5-10 us between launches, so "
+                                      "the timed region carries none); timed_region_ms_per_launch: the K launches once more with one HIP event in front "
+                                      "of and one behind them on the launch stream, / K (gaps between launches included)"}
+            # context only (SURVEY 8d asks for the measured peak beside the spec one; frac stays against the spec peak):
+            # a plain streaming read of 1 GiB with the kernel's own load pattern
+            out["roofline"]["peak_measured_read"] = caller.probe_read_bandwidth(1 << 30, 6)
+            out["roofline"]["traffic_from"] = traffic_run   # the rocprofv3 --pmc passes of tools/profile_round.sh the figure was collected in (not this run)
+            if pipelined_elapsed is not None:
+                p_ms = pipelined_elapsed / args.steps * 1e3
+                out["pipelined"] = {"streams": PIPELINE_STREAMS, "value": total_loci * args.steps / pipelined_elapsed,
+                                    "unit": "candidate loci/s", "ms_per_step": p_ms,
+                                    "hbm_frac": bytes_per_launch / (p_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                                    "note": "same steps over several HIP streams; not the contract's value, not a per-kernel roofline"}
+            if shard_check is not None:
+                out["shard_check"] = shard_check
+            # ranks that joined the collectives of this run: torch.distributed's process group (the timed region's reduce) and, N > 1, ncclCommCount
+            # of the communicator the library itself made through the C ABI (1 at N = 1: no communicator, the value is the 1-GPU path's)
+            out["rccl_ranks"] = {"torch_process_group": dist.get_world_size() if use_dist else 1,
+                                 "c_abi_comm_count": (c_abi_reduce or {}).get("ranks", caller.comm_ranks() if world == 1 else None)}
+            if c_abi_reduce is not None:
+                out["c_abi_reduce"] = c_abi_reduce
+            if config4_line is not None:
+                out["config4_strong_scaling"] = config4_line
+            if not args.no_end_to_end and world == 1:     # the drop-in boundary's own rates, rank 0 at N=1 only
+                out["end_to_end"] = end_to_end(ring[0], cfg, engine)
+                try:
+                    out["end_to_end_full"], out["roofline_streaming"] = end_to_end_full(ring[0], cfg, engine, torch)
                 except Exception as e:   # noqa: BLE001  (extra figures: they must not cost the bench line)
-                    out[key] = {"error": str(e)[:200]}
-            if not args.no_large_bam:
+                    out["end_to_end_full"] = {"error": str(e)[:200]}
                 try:
-                    out["end_to_end_full"]["from_bam_bytes_large"] = from_large_bam(cfg, engine)
-                except Exception as e:   # noqa: BLE001
-                    out["end_to_end_full"]["from_bam_bytes_large"] = {"error": str(e)[:200]}
-        if not args.no_cpu_baseline and world == 1:   # timed on rank 0 at N=1 only
-            out["cpu_baseline"], out["cpu_baseline_threads"] = cpu_baseline(torch, ring[0], cfg)
-            # the reference C# itself beside the port, when the box can run it: the probe's outcome is reported either way
-            out["cpu_baseline_reference"] = reference_csharp_baseline(ring[0], cfg)
-            # (the C# run is a process wall clock over ~6 000 loci: dotnet start-up and the genome load are inside it, so it stays under its
-            # own key and never replaces the in-process port as `cpu_baseline`)
+                    out["roofline_chain"] = chain_roofline(ring[0], cfg, engine, torch)
+                except Exception as e:   # noqa: BLE001  (extra figures: they must not cost the bench line)
+                    out["roofline_chain"] = {"error": str(e)[:200]}
+                for key, sample in (("roofline_config3", config3_sample), ("roofline_config5", config5_sample), ("roofline_config4", config4_sample)):
+                    try:
+                        out[key] = sample(engine, torch)
+                    except Exception as e:   # noqa: BLE001  (extra figures: they must not cost the bench line)
+                        out[key] = {"error": str(e)[:200]}
+                if not args.no_large_bam:
+                    try:
+                        out["end_to_end_full"]["from_bam_bytes_large"] = from_large_bam(cfg, engine)
+                    except Exception as e:   # noqa: BLE001
+                        out["end_to_end_full"]["from_bam_bytes_large"] = {"error": str(e)[:200]}
+            if not args.no_cpu_baseline and world == 1:   # timed on rank 0 at N=1 only
+                out["cpu_baseline"], out["cpu_baseline_threads"] = cpu_baseline(torch, ring[0], cfg)
+                # the reference C# itself beside the port, when the box can run it: the probe's outcome is reported either way
+                out["cpu_baseline_reference"] = reference_csharp_baseline(ring[0], cfg)
+                # (the C# run is a process wall clock over ~6 000 loci: dotnet start-up and the genome load are inside it, so it stays under its
+                # own key and never replaces the in-process port as `cpu_baseline`)
         print(json.dumps(out), flush=True)
     if c_abi_hung:   # a side thread sits in a communicator that never came up: nothing more to do in this process
         sys.stdout.flush()

@@ -229,6 +229,43 @@ def test_bench_launcher_leaves_a_launched_rank_and_n1_alone(monkeypatch, capsys)
     assert "WORLD_SIZE=2" in capsys.readouterr().err
 
 
+def test_bench_dump_outputs_writes_the_called_alleles_in_order(tmp_path, monkeypatch):
+    """`bench.py --dump-outputs DIR`: every field of the called alleles in (position, ref, alt) order and every tile's counts as float64
+    .npy files; above the size limit, the same seeded sample of alleles on every run, its rows beside it, within the limit."""
+    bench = _bench_module()
+    rng = np.random.default_rng(5)
+    n_tiles = 4
+    records = np.zeros(n_tiles * _abi.SLOTS_PER_TILE, dtype=_abi.CALLED_ALLELE_DTYPE)
+    for f in records.dtype.names:
+        records[f] = rng.integers(0, 1000, size=records[f].shape)
+    records["strand_bias_score"] = rng.normal(size=len(records))
+    tr = np.zeros(n_tiles, dtype=_abi.TILE_RESULT_DTYPE)
+    tr["record_begin"] = np.arange(n_tiles) * _abi.SLOTS_PER_TILE
+    tr["valid"] = rng.integers(0, 1 << 32, size=tr["valid"].shape, dtype=np.uint32)
+    tr["n_records"], tr["n_candidate_loci"], tr["n_called"] = rng.integers(0, 64, size=(3, n_tiles))
+    want = _abi.records_in_order(records, tr)
+
+    written = bench.dump_outputs(str(tmp_path / "all"), records, tr)
+    got = {p.stem: np.load(p) for p in (tmp_path / "all").iterdir()}
+    assert all(a.dtype == np.float64 for a in got.values()) and written == sum(a.nbytes for a in got.values())
+    assert set(got) == {f"allele_{f}" for f in want.dtype.names} | {"tile_n_records", "tile_n_candidate_loci", "tile_n_called"}
+    for f in want.dtype.names:
+        assert np.array_equal(got[f"allele_{f}"], want[f].astype(np.float64)), f
+    assert np.array_equal(got["tile_n_called"], tr["n_called"])
+
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 40_000)
+    sizes = [bench.dump_outputs(str(tmp_path / d), records, tr) for d in ("a", "b")]
+    a = {p.stem: np.load(p) for p in (tmp_path / "a").iterdir()}
+    b = {p.stem: np.load(p) for p in (tmp_path / "b").iterdir()}
+    assert sizes[0] == sizes[1] <= 40_000
+    rows = a["allele_row"].astype(np.int64)
+    assert 0 < len(rows) < len(want) and (np.diff(rows) > 0).all()
+    for k in a:
+        assert np.array_equal(a[k], b[k]), k
+    for f in want.dtype.names:
+        assert np.array_equal(a[f"allele_{f}"], want[f][rows].astype(np.float64)), f
+
+
 def _spawned_rank_script():
     return ("import os, sys, torch.distributed as dist\n"
             "dist.init_process_group('gloo')\n"
