@@ -43,7 +43,7 @@ LAST_BUILD = {"mode": None, "seconds": 0.0}   # what the last build_native of th
 
 
 def build_native(force=False, verbose=False, extra_flags=(), out=None):
-    """out != None builds a development variant (e.g. an ablation) next to the product library."""
+    """out != None builds a development variant (e.g. a -DPISCES_STORE_TIMING build) next to the product library."""
     import time
     lib = LIB if out is None else out
     if out is None and not force and not is_stale():

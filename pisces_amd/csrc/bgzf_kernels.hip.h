@@ -371,9 +371,7 @@ __device__ inline void inflate_codes(InflateStream& s, const HuffmanTable& lenco
         if (s.out_pos + total > s.out_len) { s.err = s.err ? s.err : kInflateOutputOverflow; return; }
         // where this lane's symbol writes: the bytes of the marked literals and pairs below it behind out_pos
         const int place = s.out_pos + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(lits >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)lits, 0u)) + (int)before;
-#ifndef PISCES_INFLATE_ABLATE_LIT
         if ((lits >> s.lane) & 1u) s.out[place] = (uint8_t)(X.le >> 8);
-#endif
         // a distance that reaches in front of the output (checked for all pairs at once)
         if (__builtin_amdgcn_ballot_w64(((pairs >> s.lane) & 1u) && (int)mdist > place)) { s.err = s.err ? s.err : kInflateDistanceTooFar; return; }
         // The pairs of most groups copy a few bytes each from output that older groups wrote: when no source reaches into this group's
@@ -393,18 +391,15 @@ __device__ inline void inflate_codes(InflateStream& s, const HuffmanTable& lenco
                 src_at = mine ? at - dist + k : src_at;
                 start += len;
             }
-#ifndef PISCES_INFLATE_ABLATE_COPY
             // (Measured and not kept: the load here, its store when the NEXT group is emitted, so that the load's round trip lies under
             // the next group's walk — 6.81 ms against 6.09 for 268 MB, 5.59 against 4.95 for 101 MB: the wait is not what the group
             // stands on, and the value and its place carried across the loop cost more than they hide.)
             if (s.lane < pair_bytes) s.out[dst_at] = s.out[src_at];
-#endif
         } else
         for (uint64_t mm = pairs; mm; mm &= mm - 1) {
             const int m = __builtin_ctzll(mm);
             const int len = __builtin_amdgcn_readlane((int)mlen, m), dist = __builtin_amdgcn_readlane((int)mdist, m);
             const int at = __builtin_amdgcn_readlane(place, m);
-#ifndef PISCES_INFLATE_ABLATE_COPY
             // every source byte lies before `at`, also when the pair overlaps itself (dist < len: a run of period dist).  The bytes may
             // be this wave's own stores of a moment ago: a wave's memory instructions reach the cache in program order, no wait is needed.
             const uint8_t* src = s.out + at - dist;
@@ -414,7 +409,6 @@ __device__ inline void inflate_codes(InflateStream& s, const HuffmanTable& lenco
             } else {
                 for (int k = s.lane; k < len; k += 64) dst[k] = src[k % dist];
             }
-#endif
         }
         s.out_pos += total;
     };
@@ -454,9 +448,7 @@ __device__ inline void inflate_codes(InflateStream& s, const HuffmanTable& lenco
             if (wl == 0) { s.err = kInflateBadSymbol; return true; }
             if (symbol < 256) {
                 if (s.out_pos >= s.out_len) { s.err = kInflateOutputOverflow; return true; }
-#ifndef PISCES_INFLATE_ABLATE_LIT
                 if (s.lane == 0) s.out[s.out_pos] = (uint8_t)symbol;
-#endif
                 s.out_pos++;
                 pos += wl;
                 return false;
@@ -490,7 +482,6 @@ __device__ inline void inflate_codes(InflateStream& s, const HuffmanTable& lenco
         }
         if (dist > s.out_pos) { s.err = kInflateDistanceTooFar; return true; }
         if (s.out_pos + len > s.out_len) { s.err = kInflateOutputOverflow; return true; }
-#ifndef PISCES_INFLATE_ABLATE_COPY
         const uint8_t* src = s.out + s.out_pos - dist;
         uint8_t* dst = s.out + s.out_pos;
         if (dist >= len) {
@@ -498,7 +489,6 @@ __device__ inline void inflate_codes(InflateStream& s, const HuffmanTable& lenco
         } else {
             for (int k = s.lane; k < len; k += 64) dst[k] = src[k % dist];
         }
-#endif
         s.out_pos += len;
         return false;
     };

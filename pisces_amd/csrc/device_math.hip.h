@@ -124,16 +124,6 @@ __device__ inline double gamma_series(double a, double x, double g)  // Poisson.
     double sum = 1.0 / a;
     double del = sum;
     bool done = false;
-#if defined(PISCES_SERIES_ILP) && PISCES_SERIES_ILP == 2
-    for (int i = 1; i <= 300 && !done; i += 2) {
-        const double ap0 = a + (double)i;
-        const double q0 = x / ap0, q1 = x / (ap0 + 1.0);
-        del *= q0; sum += del;
-        if (fabs(del) < fabs(sum) * kEpsilon) { done = true; break; }
-        del *= q1; sum += del;
-        if (fabs(del) < fabs(sum) * kEpsilon) { done = true; break; }
-    }
-#else
     for (int i = 1; i <= 300 && !done; i += 4) {
         const double ap0 = a + (double)i;
         const double q0 = x / ap0, q1 = x / (ap0 + 1.0), q2 = x / (ap0 + 2.0), q3 = x / (ap0 + 3.0);
@@ -146,7 +136,6 @@ __device__ inline double gamma_series(double a, double x, double g)  // Poisson.
         del *= q3; sum += del;
         if (fabs(del) < fabs(sum) * kEpsilon) { done = true; break; }
     }
-#endif
     if (done) retval = sum * exp(a * log(x) - x - g);
     return retval;
 }
@@ -211,13 +200,7 @@ __device__ inline double mathnet_gamma_ln(double z)
     const double e = 2.7182818284590452354;
     // arguments here are call counts >= 1, so only the z >= 0.5 branch is reachable
     double s = dk[0];
-#if defined(PISCES_GAMMALN_UNROLL) && PISCES_GAMMALN_UNROLL == 1
-#pragma unroll 1
-#elif defined(PISCES_GAMMALN_UNROLL) && PISCES_GAMMALN_UNROLL == 2
-#pragma unroll 2
-#else
 #pragma unroll
-#endif
     for (int i = 1; i <= 10; i++) s += dk[i] / (z + i - 1.0);
     return log(s) + log_two_sqrt_e_over_pi + ((z - 0.5) * log((z - 0.5 + r) / e));
 }

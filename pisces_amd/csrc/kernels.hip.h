@@ -119,9 +119,6 @@ __device__ __forceinline__ void stream_tuples(const uint32_t* __restrict__ tuple
 // front of every record while the chip is streaming.)
 __device__ __forceinline__ void copy_record(PiscesCalledAllele* dst, const PiscesCalledAllele* src)
 {
-#ifdef PISCES_ABLATE_STORE
-    if (src->position != -12345) return;   // development ablation: no record stores
-#endif
     const unsigned long long sb = (unsigned long long)__double_as_longlong(src->strand_bias_score);
     uint4* dp = reinterpret_cast<uint4*>(dst);
     dp[0] = make_uint4((uint32_t)src->position, (uint32_t)src->total_coverage, (uint32_t)src->allele_support, (uint32_t)src->reference_support);
@@ -300,18 +297,15 @@ __device__ inline bool process_point_allele(const PointCounts& c, int pos, int a
     if (window_level_) {
         const double werr = window_err_of_level(*window_level_, P);
         if (c.support > 0 && c.total != 0 && werr >= 0.0) vq = poisson_qscore_e(c.support, c.total, werr, P);
-    } else
-#if !(defined(PISCES_ABLATE_MATH) && (PISCES_ABLATE_MATH == 5 || PISCES_ABLATE_MATH == 9))
-    if (c.support > 0 && c.total != 0) vq = poisson_qscore(c.support, c.total, P);   // VariantQualityCalculator.Compute :11-24
-#endif
+    } else if (c.support > 0 && c.total != 0) {
+        vq = poisson_qscore(c.support, c.total, P);   // VariantQualityCalculator.Compute :11-24
+    }
     if (!isRef && vq < P.min_vq) {
         if (!kFinishAnyway) return false;
         callable = false;
     }
     SbResult sb = {0.0, 0, 0, 0};
-#if !(defined(PISCES_ABLATE_MATH) && (PISCES_ABLATE_MATH == 4 || PISCES_ABLATE_MATH == 9))
     if (c.support > 0) sb = strand_bias<kDiploidOk>(c.cov, c.sup, P);                // StrandBiasCalculator.Compute :10-15
-#endif
     finish_allele(c, pos, a, isRef, rt, vq, sb, ref, win_lo, win_hi, P, r, s_refwin, s_refidx, pre_tail, nullptr, window_level_);
     return callable;
 }
@@ -395,17 +389,9 @@ __device__ inline void call_roles(const int* hist, const uint32_t* gapped /* LDS
             const PointCounts c = point_counts(hist, l, a, false, rt, g);
             const int slot = l * 4 + k;
             if (wave == 1) {
-#if defined(PISCES_ABLATE_MATH) && (PISCES_ABLATE_MATH == 9 || PISCES_ABLATE_MATH == 6)
-                vs->vq[slot] = 100;
-#else
                 vs->vq[slot] = !(c.support > 0 && c.total != 0) ? 0 : !s_lvl ? poisson_qscore(c.support, c.total, P)
                                : s_lvl[l] != kNoLevel ? poisson_qscore_e(c.support, c.total, window_err_of_level(s_lvl[l], P), P) : 0;
-#endif
-#if defined(PISCES_ABLATE_MATH) && (PISCES_ABLATE_MATH == 9 || PISCES_ABLATE_MATH == 7)
-            } else if (c.support < 0) {
-#else
             } else if (c.support > 0) {
-#endif
                 const SbStats ov = sb_stats_of<true>(0, c.cov, c.sup, P), fw = sb_stats_of<true>(1, c.cov, c.sup, P),
                               rv = sb_stats_of<true>(2, c.cov, c.sup, P);
                 vs->ov_var[slot] = ov.var_gt_zero;
@@ -517,20 +503,9 @@ __global__ __launch_bounds__(kBlock, 4) void call_tiles_kernel(
     __syncthreads();
 
     const uint32_t n_loci = (uint32_t)tile.n_loci, min_bq = (uint32_t)P.min_bq;
-#if defined(PISCES_ABLATE) && PISCES_ABLATE == 2
-    // development ablation: loads only (no LDS atomics, no call phase)
-    uint32_t acc = 0;
-    stream_tuples(tuples, tile.tuple_begin, tile.tuple_end, [&](uint32_t v) { acc ^= v; });
-    if (acc == 0x12345u) hist[threadIdx.x] = (int)(n_loci + min_bq);
-#else
     stream_tuples(tuples, tile.tuple_begin, tile.tuple_end,
                   [&](uint32_t v) { accumulate_folded(hist, v, n_loci, min_bq); });
-#endif
     __syncthreads();
-#if defined(PISCES_ABLATE) && PISCES_ABLATE >= 1
-    // development ablation: no call phase
-    if (threadIdx.x == 0) { tile_results[t].record_begin = 0; tile_results[t].n_records = hist[5]; }
-#else
 #ifdef PISCES_TIMING
     const long long tc1 = wall_clock64();
 #endif
@@ -542,7 +517,6 @@ __global__ __launch_bounds__(kBlock, 4) void call_tiles_kernel(
         tile_results[t].n_records = (int)(tc1 & 0x3FFFFFFF);         // stream end
         tile_results[t].n_candidate_loci = (int)(tc2 & 0x3FFFFFFF);  // call end
     }
-#endif
 #endif
 }
 
@@ -869,24 +843,12 @@ __global__ __launch_bounds__(64 * NW, NW == 1 ? PISCES_WAVE_OCC : PISCES_WAVE2_O
     {
         // single-round launches (NW = 2): streaming waves win the issue arbitration over waves in their call phase — the launch
         // ends with the slowest tile, and a tile that is still streaming has its whole call phase ahead of it
-#ifndef PISCES_NO_PRIO
         if (NW == 2) __builtin_amdgcn_s_setprio(3);
-#endif
         const uint32_t min_bq_shifted = (uint32_t)min(max(P.min_bq, 0), 255) << 24;
-#if defined(PISCES_ABLATE) && PISCES_ABLATE == 2
-        uint32_t acc = 0;   // development ablation: loads only
-        stream_tuples_wave<NW>(tuples, tile.tuple_begin, tile.tuple_end, l, wid, [&](uint32_t v) { acc ^= v; }, setup);
-        if (acc == 0x12345u) hist[l] = (int)min_bq_shifted;
-#else
         stream_tuples_wave<NW>(tuples, tile.tuple_begin, tile.tuple_end, l, wid, [&](uint32_t v) { accumulate_wave(hist, v, min_bq_shifted); }, setup);
-#endif
     }
     __syncthreads();
     if (NW == 2) __builtin_amdgcn_s_setprio(0);
-#if defined(PISCES_ABLATE) && PISCES_ABLATE >= 1
-    if (threadIdx.x == 0) { tile_results[t].record_begin = 0; tile_results[t].n_records = hist[5 + l]; }
-    return;
-#endif
 #ifdef PISCES_TIMING
     const long long tc1 = wall_clock64();
 #endif

@@ -332,7 +332,6 @@ struct PiscesHip {
     DeviceBuf<PiscesCalledAllele> d_compact;
     int kernel_variant = 4;    // 4 = auto (two waves per tile while every tile of the launch is resident at once, else one),
                                // 2 = one wave per tile, 3 = two waves per tile, 0 = one 4-wave workgroup per tile
-    int lds_pad = 0;           // development: extra dynamic LDS per workgroup (occupancy experiments)
     std::string err;
 
     DeviceBuf<uint8_t> d_ref;
@@ -553,12 +552,9 @@ struct PiscesHip {
     std::vector<hipGraphExec_t> graphs;       // pisces_hip_call_tiles_graph_build
     std::vector<hipGraph_t> graph_defs;
     int store_waves = 0;                      // development: waves per tile of call_store_tiles_kernel (PISCES_HIP_STORE_WAVES; 0 = by launch size)
-    int tile_order = 2;                       // which tile a workgroup of call_store_tiles_kernel takes in a launch of several tiles a CU (PISCES_HIP_TILE_ORDER): 2 tiles
-                                              // traded by price inside small groups (exchanged_tile), 1 tile_order_kernel's order (a launch in front), 0 position order
-    DeviceBuf<int32_t> d_tile_order;
-    bool store_prio = true;                   // PISCES_HIP_STORE_PRIO=0: no issue priority for the walking waves of call_store_tiles_kernel (the A / B)
-    int finder_wave = 0;                      // PISCES_HIP_FINDER: the default is a lane a read, events first; =bases: a lane a read, base by base (round 3's);
-                                              // =wave / =batch: a wave for one / for 64 reads (finder_kernels.hip.h; measured slower)
+    bool trade_tiles = true;                  // which tile a workgroup of call_store_tiles_kernel takes in a launch of several tiles a CU: tiles traded by price
+                                              // inside small groups (exchanged_tile), or position order (PISCES_HIP_TILE_ORDER=0)
+    bool finder_bases = false;                // PISCES_HIP_FINDER=bases: the candidate walk a lane a read, base by base (round 3's), not events first
     DeviceBuf<long long> d_scan_sums;         // block sums of launch_found_scan
     bool device_genotyper = true;             // PISCES_HIP_DEVICE_GENOTYPER=0: diploid / haploid genotypes are always the host pass of the flush (the A / B of the tests)
     bool merge_in_place = true;               // PISCES_HIP_MERGE_IN_PLACE=0: the candidate kernel's rows and the tile kernels' are merged into a vector of their own (the A / B of the tests)
@@ -573,8 +569,6 @@ struct PiscesHip {
     struct DeferredGrid { ShapeArgs S; unsigned blocks; };
     std::vector<DeferredGrid> deferred_grid;  // grid roles of read_shape_kernel kept back until something reads or changes a grid (store_run_deferred)
     int32_t tile_loci = 0;                    // PISCES_HIP_TILE_LOCI: loci a tile of a regular flush (development; 0 = 64)
-    int32_t stream_wgs_per_cu = 0;            // add_fused_kernel: > 0 = that many persistent stream workgroups a CU in front of the read role (PISCES_HIP_STREAM_WGS_PER_CU)
-    int32_t role_stride = 1;                  // add_fused_kernel: every n-th workgroup at the front of the launch is a read workgroup (PISCES_HIP_ROLE_STRIDE)
     bool defer_grid = true;                   // PISCES_HIP_DEFER_GRID=0: enqueued by the add itself (the A / B)
 #ifdef PISCES_ADD_STAMPS
     DeviceBuf<long long> d_add_stamps;
@@ -898,14 +892,12 @@ int32_t pisces_hip_create(const PiscesHipConfig* cfg, int32_t device, PiscesHip*
         if (kv && std::string(kv) == "wave2") h->kernel_variant = 3;
         if (kv && std::string(kv) == "auto") h->kernel_variant = 4;
         if (kv && std::string(kv) == "block") h->kernel_variant = 0;
-        if (const char* lp = getenv("PISCES_HIP_LDS_PAD")) h->lds_pad = atoi(lp);
         h->prof_on = getenv("PISCES_HIP_HOST_PROFILE") != nullptr;
         const char* rp = getenv("PISCES_HIP_READ_PATH");   // "log": reads are expanded into the observation log and bucketed at flush time (the earlier chain)
         if (rp && std::string(rp) == "log") h->read_path = 0;
         if (const char* v = getenv("PISCES_HIP_STORE_DIRECT_BYTES")) h->store_direct_bytes = (size_t)std::max(0ll, atoll(v));
         if (const char* v = getenv("PISCES_HIP_STORE_WAVES")) h->store_waves = atoi(v);
-        if (const char* v = getenv("PISCES_HIP_TILE_ORDER")) h->tile_order = atoi(v);
-        if (const char* v = getenv("PISCES_HIP_STORE_PRIO")) h->store_prio = atoi(v) != 0;
+        if (const char* v = getenv("PISCES_HIP_TILE_ORDER")) h->trade_tiles = atoi(v) != 0;
         if (const char* v = getenv("PISCES_HIP_DEVICE_MERGE")) h->device_merge = atoi(v) != 0 ? 1 : 0;   // the A/B of tests/test_read_store.py
         // MNV calling on: the split form, unless the candidate records are asked to come back unmerged (PISCES_HIP_DEVICE_MERGE=0: the
         // earlier form, every candidate an object on the host, the tile kernels Reference records only) or PISCES_HIP_MNV_SPLIT=0
@@ -915,13 +907,11 @@ int32_t pisces_hip_create(const PiscesHipConfig* cfg, int32_t device, PiscesHip*
         if (const char* v = getenv("PISCES_HIP_STORE_SEAL_BYTES")) h->store_seal_bytes = (size_t)std::max(0ll, atoll(v));
         if (const char* v = getenv("PISCES_HIP_DEVICE_CHECKS")) h->device_checks = atoi(v) != 0 ? 1 : 0;
         if (const char* v = getenv("PISCES_HIP_TILE_LOCI")) h->tile_loci = atoi(v);
-        if (const char* v = getenv("PISCES_HIP_STREAM_WGS_PER_CU")) h->stream_wgs_per_cu = std::max(0, atoi(v));
-        if (const char* v = getenv("PISCES_HIP_ROLE_STRIDE")) h->role_stride = std::max(1, atoi(v));
         if (const char* v = getenv("PISCES_HIP_DEFER_GRID")) h->defer_grid = atoi(v) != 0;
         if (const char* v = getenv("PISCES_HIP_COMPACT")) h->compact_mode = std::string(v) == "two" ? 2 : std::string(v) == "lookback" ? 3 : 0;
         if (const char* v = getenv("PISCES_HIP_MERGE_IN_PLACE")) h->merge_in_place = atoi(v) != 0;
         if (const char* v = getenv("PISCES_HIP_DEVICE_GENOTYPER")) h->device_genotyper = atoi(v) != 0;
-        if (const char* v = getenv("PISCES_HIP_FINDER")) h->finder_wave = std::string(v) == "wave" ? 1 : std::string(v) == "batch" ? 2 : std::string(v) == "bases" ? 3 : 0;
+        if (const char* v = getenv("PISCES_HIP_FINDER")) h->finder_bases = std::string(v) == "bases";
     }
     {
         // MathOperations.QtoP(q) = Math.Pow(10, -1 * q / 10f) for every integer q-score the caller can produce
@@ -1075,7 +1065,7 @@ int32_t pisces_hip_destroy(PiscesHip* h)
     }
     h->d_summary.release();
     h->d_ref.release(); h->d_tuples.release(); h->d_tiles.release(); h->d_tile_results.release();
-    h->d_records.release(); h->d_counts.release(); h->d_gapped.release(); h->d_count.release(); h->d_totals.release(); h->d_qlut.release(); h->d_bq_lut.release(); h->d_sumq_fix.release(); h->d_sumq.release(); h->d_gq_tail.release(); h->d_vq_tab.release(); h->d_sb_tab.release(); h->d_sb0_tab.release(); h->d_gq_cap.release(); h->d_params.release(); h->d_offsets.release(); h->d_compact.release(); h->d_tile_order.release();
+    h->d_records.release(); h->d_counts.release(); h->d_gapped.release(); h->d_count.release(); h->d_totals.release(); h->d_qlut.release(); h->d_bq_lut.release(); h->d_sumq_fix.release(); h->d_sumq.release(); h->d_gq_tail.release(); h->d_vq_tab.release(); h->d_sb_tab.release(); h->d_sb0_tab.release(); h->d_gq_cap.release(); h->d_params.release(); h->d_offsets.release(); h->d_compact.release();
     for (int i = 0; i < 2; i++) { h->d_log_pos[i].release(); h->d_log_tup[i].release(); }
     h->d_log_n.release(); h->d_flags.release(); h->d_bucket.release(); h->d_total.release();
     for (auto& st : h->stage) {

@@ -38,9 +38,6 @@
 #else
 #define PISCES_STAMP(k, is_max) do { } while (0)
 #endif
-#ifndef PISCES_ADD_ABLATE
-#define PISCES_ADD_ABLATE 0   // (development: ablations of add_fused_kernel, tools/add_ablate.sh)
-#endif
 namespace pisces {
 
 struct ReadDesc {       // 16 bytes, one per read, in position order
@@ -351,7 +348,7 @@ __device__ __forceinline__ void shape_reads(const ShapeArgs& A, const int block,
     for (int d = 32; d >= 1; d >>= 1) reach = max(reach, __shfl_xor(reach, d, 64));
     const bool any_unsorted = __ballot(unsorted) != 0ull, any_complex = __ballot(complex_read) != 0ull;
     const int frag_bits = (__ballot(generic_read) != 0ull ? 1 : 0) | (__ballot(has_del) != 0ull ? 2 : 0);
-    if ((threadIdx.x & 63) == 0 && PISCES_ADD_ABLATE != 9) {
+    if ((threadIdx.x & 63) == 0) {
         // (plain reads first: same-address atomics from the whole chip are what they cost, and after the first few waves none is needed)
         if (reach > A.state[kStateReach]) atomicMax(&A.state[kStateReach], reach);
         if (any_unsorted && A.state[kStateUnsorted] == 0) atomicOr(&A.state[kStateUnsorted], 1);
@@ -402,9 +399,6 @@ constexpr int kPrepReplicas = 32;
 // show zero for the rest of the launch) costs no atomic: same-address atomics from eight XCDs serialise at 0.1-0.2 us each
 __device__ __forceinline__ void set_keys(const PrepareArgs& A, int replica, int64_t a, int64_t b)
 {
-#if PISCES_ADD_ABLATE == 7
-    return;
-#endif
     uint32_t* const map = A.block_bits + (int64_t)(replica & (kPrepReplicas - 1)) * A.map_stride;   // (any copy will do: the read workgroup's index)
     for (int64_t k = a; k <= b; k++) {
         if (k >= A.n_block_bits) continue;   // (cannot be: the map covers every int32 position)
@@ -553,7 +547,7 @@ __device__ __forceinline__ void prepare_reads(const PrepareArgs& A, const int bl
             if (!seen) set_keys(A, block, s_run_a[t], s_run_b[t]);
         }
     }
-    if (threadIdx.x == 0 && PISCES_ADD_ABLATE != 8) {
+    if (threadIdx.x == 0) {
         int32_t* const span = A.key_span + 4 * (int)(block & (kPrepReplicas - 1));
         // (no look before the atomics either: four of them a workgroup on the copy of its index, none waited for)
         (void)__hip_atomic_fetch_min(&span[2], s_plo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -667,8 +661,6 @@ struct AddFusedArgs {
     ShapeArgs S;                // shape role (do_shape) — reads the same arrays; S.enc_* unused here
     int32_t do_shape;
     int32_t read_blocks, stream_blocks, misc_blocks;
-    int32_t role_stride;        // every role_stride-th unit of eight workgroups is a read unit (>= 1), until there are read_blocks read workgroups
-    int32_t stream_first;       // != 0: the stream and misc workgroups are the launch's first, the read workgroups follow
     const uint8_t* s_bases;     // stream role: sources
     const uint8_t* s_quals;
     const uint8_t* s_dirs;      // or nullptr
@@ -700,9 +692,6 @@ __device__ __forceinline__ void add_stream_roles(const AddFusedArgs& A, const in
 {
         if (sb < A.stream_blocks) {
             // ---- stream role
-#if PISCES_ADD_ABLATE == 1
-            return;
-#endif
             PISCES_STAMP(0, false);
             const uint32_t qk4 = (0x7Fu + A.enc_min_bq) * 0x01010101u;
             const int64_t n16 = A.n_seq >> 4;
@@ -731,16 +720,10 @@ __device__ __forceinline__ void add_stream_roles(const AddFusedArgs& A, const in
                         for (int k = 0; k < 4; k++) bad_dir = bad_dir || ((dw[k] + 0x7D7D7D7Du) | dw[k]) & 0x80808080u;   // some byte > 2
                         if (A.d_dirs) __builtin_memcpy(A.d_dirs + 16 * i, dw, 16);
                     }
-#if PISCES_ADD_ABLATE == 5
-                    if (bw[p][0] == 0x12345678u && qw[p][1] == 0x9ABCDEF0u) __builtin_memcpy(A.d_codes + 16 * i, bw[p], 16);
-                    continue;
-#endif
-#if PISCES_ADD_ABLATE != 4
                     if (A.d_bases) {
                         __builtin_memcpy(A.d_bases + 16 * i, bw[p], 16);
                         __builtin_memcpy(A.d_quals + 16 * i, qw[p], 16);
                     }
-#endif
                     if (A.d_codes) {
                         uint32_t c[4];
 #pragma unroll
@@ -778,29 +761,14 @@ __device__ __forceinline__ void add_stream_roles(const AddFusedArgs& A, const in
 }
 __global__ __launch_bounds__(256, PISCES_ADD_OCC) void add_fused_kernel(AddFusedArgs A)
 {
-    // Roles by workgroup index.  stream_first > 0: the launch's FIRST workgroups are the stream (and misc) role — a few persistent ones a CU
-    // that walk the batch's bytes from the launch's first microsecond to its last with 8 KB a wave in flight — and the read workgroups
-    // follow in index order (which is dispatch order: their scan waits for lower read indices only) into the slots that are left.  With the
-    // read role in front (stream_first == 0; every role_stride-th unit of eight workgroups — one per XCD — a read unit, until there are
-    // read_blocks of them) its workgroups take 85 % of the chip's wave slots for ~35 us of round trips and the launch's bytes wait for them.
-    const int raw = (int)blockIdx.x;
-    bool read_role;
-    int b;   // the index inside its role(s)
-    if (A.stream_first) {
-        const int front = A.stream_blocks + A.misc_blocks;
-        read_role = raw >= front;
-        b = read_role ? raw - front : raw;
-    } else {
-        const int unit = raw >> 3, in_unit = raw & 7;
-        const int uq = unit / A.role_stride;
-        const bool read_unit = unit - uq * A.role_stride == 0;
-        const int reads_before = min(A.read_blocks, ((unit + A.role_stride - 1) / A.role_stride) * 8 + (read_unit ? in_unit : 0));
-        read_role = read_unit && uq * 8 + in_unit < A.read_blocks;
-        b = read_role ? uq * 8 + in_unit : raw - reads_before;
-    }
+    // Roles by workgroup index: the read role in front, in index order (which is dispatch order: its scan waits for lower read indices
+    // only), then the stream and misc roles.  Its workgroups take 85 % of the chip's wave slots for ~35 us of round trips and the launch's
+    // bytes wait for them; the stream role in front, or read units spread between the streaming workgroups by XCD, were measured and were
+    // no faster.
+    const int b = (int)blockIdx.x;   // the read workgroup's index
     __shared__ int s_wf[4], s_wp[4], s_excl[2], s_last;
-    if (!read_role) {
-        add_stream_roles(A, b);
+    if (b >= A.read_blocks) {
+        add_stream_roles(A, b - A.read_blocks);
         // (the streaming roles leave nothing the collecting workgroup reads: no fence, no count — a release fence here is a write-back of the
         // XCD's whole L2, and 8 000 workgroups x 4 waves of them made the launch 1.2 ms where its bytes take 45 us)
         return;
@@ -811,15 +779,9 @@ __global__ __launch_bounds__(256, PISCES_ADD_OCC) void add_fused_kernel(AddFused
     bool ok;
     PISCES_STAMP(2, false);
     PISCES_STAMP(3, true);
-#if PISCES_ADD_ABLATE == 6
-    found = pool = 0; ok = true;
-#else
     prepare_reads(A.P, b, found, pool, ok);
-#endif
     PISCES_STAMP(4, true);
-#if PISCES_ADD_ABLATE != 2
     if (A.do_shape) shape_reads(A.S, b, ok);
-#endif
     PISCES_STAMP(5, true);
     // the candidate-record slots: exclusive scan over the batch's reads, in this launch
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -870,9 +832,6 @@ __global__ __launch_bounds__(256, PISCES_ADD_OCC) void add_fused_kernel(AddFused
         } else {
             if (lane == 0) __hip_atomic_store(&A.scan_state[b], kScanAggregate | mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             int base = b - 1;   // lane l looks at workgroup base - l
-#if PISCES_ADD_ABLATE == 3
-            base = -1000000;
-#endif
             for (;;) {
                 const int idx = base - lane;
                 const unsigned long long w = idx >= 0 ? __hip_atomic_load(&A.scan_state[idx], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : kScanInclusive;
@@ -915,9 +874,6 @@ __global__ __launch_bounds__(256, PISCES_ADD_OCC) void add_fused_kernel(AddFused
     // acknowledged before thread 0 counts the workgroup in: the count is a RELAXED atomic.  (A release there is a write-back of the XCD's
     // whole L2 — while the stream role fills it — per read workgroup: 60 us of the launch's 127; a fence in every wave of every role: 1.2 ms.)
     // The collector reads with agent-scope atomic loads.
-#if PISCES_ADD_ABLATE == 10
-    return;
-#endif
     __syncthreads();
     if (threadIdx.x == 0) {
         // counted in two levels — kPrepReplicas counters by workgroup index, then one for the counters that are full — so that no word sees
@@ -1375,11 +1331,7 @@ __device__ __forceinline__ void walk_segment_fast(const SegmentView& G, int tile
                 at = e.y + (uint32_t)(rel8 >> 3);   // the byte on the lane's first locus (up to 7 before the read's first, 63 behind its last: kSegmentPad)
                 U.ex = e.x;
             }
-#if defined(PISCES_STORE_ABLATE) && PISCES_STORE_ABLATE == 5
-            const unsigned long long c8 = 0x0004080C0004080Cull + (at & 1u);   // development ablation: no loads of codes
-#else
             const unsigned long long c8 = load_u64_unaligned(codes + at);
-#endif
             U.cw[0] = (uint32_t)c8; U.cw[1] = (uint32_t)(c8 >> 32);
             if (kDirs) {
                 const unsigned long long d8 = load_u64_unaligned(dirs + at);
@@ -1390,10 +1342,6 @@ __device__ __forceinline__ void walk_segment_fast(const SegmentView& G, int tile
             const uint32_t m0 = (uint32_t)U.m, m1 = (uint32_t)(U.m >> 32);   // the lane's bytes on the read
             const uint32_t d0 = kDirs ? U.dw[0] : __builtin_amdgcn_perm(U.ex, U.ex, 0x03030303u), d1 = kDirs ? U.dw[1] : d0;   // (the pair's direction in every byte)
             const uint32_t r0 = (m0 & (U.cw[0] | d0)) | (~m0 & 0x18181818u), r1 = (m1 & (U.cw[1] | d1)) | (~m1 & 0x18181818u);
-#if defined(PISCES_STORE_ABLATE) && PISCES_STORE_ABLATE == 2
-            if ((r0 ^ r1) == 0x12345u) *reinterpret_cast<volatile int*>(hbytes) = 1;   // development ablation: no histogram update
-            return;
-#endif
             const uint32_t cl = decltype(right)::value ? col_lo_r : col_lo_l, ch = decltype(right)::value ? col_hi_r : col_hi_l;
             const uint32_t lo8 = __builtin_amdgcn_perm(r1, r0, rot_lo), hi8 = __builtin_amdgcn_perm(r1, r0, rot_hi);   // the eight row bytes rotated right by rot bytes
 #pragma unroll
@@ -1531,82 +1479,11 @@ __device__ __forceinline__ int xcd_tile_of_block(int b, int n)
 // THE ORDER OF A LAUNCH'S TILES (launches of several tiles a CU).  A launch ends with the CU that was dealt the most fragments: a tile
 // across two amplicons lists twice the fragments of one inside an amplicon, and with the tiles taken in position order the tiles one
 // CU is dealt lie a fixed distance apart — on a periodic panel they are all of one kind (config 2: 3 000 to 6 000 fragments a CU, mean
-// 4 400; the launch lasted as long as the 6 000).  tile_order_kernel prices every tile (the fragments in its range: the two grid
-// entries walk_segment_fast's search reads, + the bucketed tuples) and, inside each XCD's share of the tiles (xcd_tile_of_block: neighbours
-// stay on one L2), orders them by falling cost, the rounds of `cus` workgroups alternately forwards and backwards: the workgroups
-// of a round go to different CUs, so every CU gets one tile of every cost stratum.  order[b] = the tile of workgroup b.  Which tile a
-// workgroup takes changes no result (a tile's records lie in the tile's own slots).  Measured (config 2, 1 600 tiles, profiles/
-// r05_tile_order.txt): the flush kernel 32.0-32.7 us against 35.9-37.8 in position order (fragments of the fullest CU 5 000 against
-// 6 000) — and 8.6-9.6 us for this launch in front of it (two dependent round trips on an idle chip and the launch itself), so a
-// flush is slower by ~5 us: NOT the default (PISCES_HIP_TILE_ORDER=1 asks for it); the default is exchanged_tile below.
-__device__ __forceinline__ int tile_cost(const StoreView& S, const PiscesTile& tile)
-{
-    int cost = (int)min((long long)(tile.tuple_end - tile.tuple_begin) >> 4, 0x3FFFFFll);
-    const int tile_end = tile.start_position + kTile - 1;
-    for (int sg = 0; sg < S.n_segments; sg++) {
-        const SegmentView& G = S.seg[sg];
-        if (G.n_frags <= 0 || G.state[kStateUnsorted] != 0 || !G.grid || (G.state[kStateFrags] & kGridBadBit)) continue;   // (the same for every tile)
-        const int reach = G.state[kStateReach];
-        const int x_lo = (int)max((long long)tile.start_position - reach + 1, -0x7FFFFFFFll), x_hi = tile_end == 0x7FFFFFFF ? 0x7FFFFFFF : tile_end + 1;
-        int e[2];
-#pragma unroll
-        for (int k2 = 0; k2 < 2; k2++) {
-            const long long k = (long long)max(k2 ? x_hi : x_lo, 0) - G.grid_base;
-            e[k2] = k < 0 ? 0 : G.n_frags;
-            if (k >= 0 && k < G.grid_n) e[k2] = min(G.grid[k], G.n_frags);
-        }
-        cost += min(max(e[1] - e[0], 0), 0x3FFFFF);
-    }
-    return cost;
-}
-constexpr int kTileFixedCost = 1264;   // a tile's search, pipeline fill / drain and call phase in units of one listed fragment (13.4 us against 10.6 ns, config 2)
-constexpr int kOrderCached = 2048;      // tiles of an XCD whose costs tile_order_kernel keeps in LDS (beyond: priced again in each pass)
-__global__ __launch_bounds__(256) void tile_order_kernel(StoreView S, const PiscesTile* __restrict__ tiles /* or nullptr: R */, RegularTiles R, int32_t n_tiles,
-                                                         int32_t cus /* CUs of an XCD */, int32_t* __restrict__ order)
-{
-    __shared__ int s_max, s_cnt[256], s_at[256], s_wave[4], s_cost[kOrderCached];
-    const int x = (int)blockIdx.x, q = n_tiles >> 3, rem = n_tiles & 7, tid = (int)threadIdx.x;
-    const int first = x * q + min(x, rem), cnt = q + (x < rem ? 1 : 0);
-    if (tid == 0) s_max = 1;
-    s_cnt[tid] = 0;
-    __syncthreads();
-    auto price = [&](int j) { return kTileFixedCost + tile_cost(S, tiles ? tiles[first + j] : regular_tile(R, first + j)); };
-    for (int j = tid; j < cnt; j += 256) {
-        const int c = price(j);
-        if (j < kOrderCached) s_cost[j] = c;
-        atomicMax(&s_max, c);
-    }
-    __syncthreads();
-    const long long mx = s_max;
-    auto bucket_of = [&](int j) { const int c = j < kOrderCached ? s_cost[j] : price(j); return 255 - (int)((long long)c * 255 / mx); };   // the dearest tiles first
-    for (int j = tid; j < cnt; j += 256) atomicAdd(&s_cnt[bucket_of(j)], 1);
-    __syncthreads();
-    {   // exclusive scan of the 256 bucket counts
-        const int v = s_cnt[tid];
-        int a = v;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) { const int u = __shfl_up(a, d); if ((tid & 63) >= d) a += u; }
-        if ((tid & 63) == 63) s_wave[tid >> 6] = a;
-        __syncthreads();
-        int base = 0;
-        for (int w = 0; w < (tid >> 6); w++) base += s_wave[w];
-        s_at[tid] = base + a - v;
-    }
-    __syncthreads();
-    // workgroup j of the XCD runs on CU j % cus (the dispatcher deals them in turn): the r CUs that get one tile more than the others take
-    // the cheapest tiles, the others share the dearest — each group by rounds that run alternately forwards and backwards
-    const int s = cnt / cus, r = cnt - s * cus, n6 = cus - r, n_top = s * n6;
-    for (int j = tid; j < cnt; j += 256) {
-        const int rank = atomicAdd(&s_at[bucket_of(j)], 1);
-        int k, c;
-        if (rank < n_top) { k = rank / n6; const int i = rank - k * n6; c = r + ((k & 1) ? n6 - 1 - i : i); }
-        else { const int rr = rank - n_top; k = rr / r; const int i = rr - k * r; c = (k & 1) ? r - 1 - i : i; }
-        order[(k * cus + c) * 8 + x] = first + j;
-    }
-}
-
-// A little of that without a launch in front: the workgroups of one round of an XCD trade tiles inside small groups.  Workgroup j of
-// an XCD runs on CU j % cus (the dispatcher deals them in turn), so the first r = cnt % cus CUs get one tile more than the others; each
+// 4 400; the launch lasted as long as the 6 000).  Every tile priced and dealt by cost in a launch in front of the flush kernel made the
+// kernel faster but the flush slower: the extra launch costs more than it saves.  So, without a launch in
+// front: the workgroups of one round of an XCD trade tiles inside small groups.  Which tile a workgroup takes changes no result (a
+// tile's records lie in the tile's own slots).  Workgroup j of an XCD runs on CU j % cus (the dispatcher deals them in turn), so the
+// first r = cnt % cus CUs get one tile more than the others; each
 // of them forms a group with g - 1 of the others (g = cus / r, at most 8).  Every workgroup of a group prices the g tiles of the group
 // (the 2 g grid entries are one load instruction of the wave, lanes 0 .. g - 1 the low ends, 32 .. 32 + g - 1 the high ends: a tile's
 // start keeps its two dependent round trips, and the range of the tile taken goes to walk_segment_fast, which then has no search of
@@ -1688,7 +1565,7 @@ __device__ __forceinline__ uint32_t allele_row_bytes_of_base(uint32_t c)
 template <int NW>
 __global__ __launch_bounds__(64 * NW, NW == 1 ? PISCES_WAVE_OCC : PISCES_WAVE2_OCC) void call_store_tiles_kernel(
     StoreView S, const uint32_t* __restrict__ tuples, const PiscesTile* __restrict__ tiles /* or nullptr: R */, RegularTiles R, int32_t n_tiles,
-    const int32_t* __restrict__ order /* tile_order_kernel's, or nullptr: position order */, int32_t trade_cus /* > 0: exchanged_tile */, int32_t walk_prio, const uint8_t* __restrict__ ref, int32_t ref_start, int64_t ref_len, PiscesCalledAllele* __restrict__ records,
+    int32_t trade_cus /* > 0: exchanged_tile */, int32_t walk_prio, const uint8_t* __restrict__ ref, int32_t ref_start, int64_t ref_len, PiscesCalledAllele* __restrict__ records,
     PiscesTileResult* __restrict__ tile_results, DeviceParams P, const DeviceParams* __restrict__ Pd)
 {
     __shared__ __attribute__((aligned(16))) int hist[2 * kWaveRegion];   // [region: quality-passing / low-quality][allele * 4 + direction][locus]
@@ -1699,20 +1576,13 @@ __global__ __launch_bounds__(64 * NW, NW == 1 ? PISCES_WAVE_OCC : PISCES_WAVE2_O
 
     if ((int)blockIdx.x >= n_tiles) return;
     int pre_lo = -1, pre_hi = 0;
-#ifdef PISCES_STORE_NO_SWIZZLE
-    const int t = (int)blockIdx.x;
-#else
-    const int t = order ? order[blockIdx.x] : trade_cus > 0 ? exchanged_tile(S, tiles, R, n_tiles, trade_cus, (int)blockIdx.x, (int)(threadIdx.x & 63), &pre_lo, &pre_hi)
-                                            : xcd_tile_of_block((int)blockIdx.x, n_tiles);
-#endif
+    const int t = trade_cus > 0 ? exchanged_tile(S, tiles, R, n_tiles, trade_cus, (int)blockIdx.x, (int)(threadIdx.x & 63), &pre_lo, &pre_hi)
+                                : xcd_tile_of_block((int)blockIdx.x, n_tiles);
     const int l = threadIdx.x & 63, wid = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const PiscesTile tile = tiles ? tiles[t] : regular_tile(R, t);
 #ifdef PISCES_STORE_TIMING
     const long long tc0 = wall_clock64();   // 100 MHz, chip-global
     long long stamps[6] = {0, 0, 0, 0, 0, 0};   // [2..5]: shader-clock cycles this wave spent issuing / consuming / trimming, loop iterations
-#endif
-#if defined(PISCES_STORE_ABLATE) && PISCES_STORE_ABLATE == 4
-    if (tile.n_loci > 0) { if (threadIdx.x == 0) { tile_results[t].record_begin = 0; tile_results[t].n_records = 0; tile_results[t].n_called = 0; tile_results[t].n_candidate_loci = 0; } return; }   // development ablation: nothing
 #endif
     {
         int4* h4 = reinterpret_cast<int4*>(hist);
@@ -1764,10 +1634,6 @@ __global__ __launch_bounds__(64 * NW, NW == 1 ? PISCES_WAVE_OCC : PISCES_WAVE2_O
     const long long tc_walk = wall_clock64();
 #endif
     __syncthreads();
-#if defined(PISCES_STORE_ABLATE) && (PISCES_STORE_ABLATE == 1 || PISCES_STORE_ABLATE == 2 || PISCES_STORE_ABLATE >= 5)
-    if (threadIdx.x == 0) { tile_results[t].record_begin = 0; tile_results[t].n_records = hist[5 + l] & 0; tile_results[t].n_called = 0; tile_results[t].n_candidate_loci = 0; }   // development ablation: no call phase
-    return;
-#endif
     if (NW > 2 && wid != 0 && wid != NW - 1) return;
     if (walk_prio) __builtin_amdgcn_s_setprio(0);
     call_phase_wave<(NW == 1 ? 1 : 2), HistLinear>(hist, s_refwin, s_vmask, tile, t, l, NW == 1 ? 0 : (wid == NW - 1 ? 1 : 0), ref, ref_start, ref_len, records, tile_results, P

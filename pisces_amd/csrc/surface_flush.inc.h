@@ -177,7 +177,6 @@ static hipError_t launch_call_tiles(PiscesHip* h, hipStream_t s, const uint32_t*
                               const uint8_t* d_ref, int32_t ref_start, int64_t ref_len, PiscesCalledAllele* d_records,
                               PiscesTileResult* d_tr, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr)
 {
-    const uint32_t lds = (uint32_t)h->lds_pad;
     if (h->cfg.noise_model == PISCES_NOISE_WINDOW) {
         // NoiseModel.Window needs the base-quality sums next to the counts, cell by cell (RegionState.cs:61): anchor-resolved counts and
         // sums go to HBM (accumulate_tiles_kernel) and the call phase reads them back (call_counts_kernel).  Not the streaming-rate
@@ -199,20 +198,20 @@ static hipError_t launch_call_tiles(PiscesHip* h, hipStream_t s, const uint32_t*
         const bool two = h->kernel_variant == 3 || (h->kernel_variant == 4 && (int64_t)n_tiles <= (int64_t)h->n_cus * 32);
         // (without events the plain launch: it is what a stream capture records as a kernel node)
         if (!two && !e0 && !e1)
-            hipLaunchKernelGGL(call_tiles_wave_kernel<1>, dim3((unsigned)n_tiles), dim3(64), lds, s, d_tuples, d_tiles, n_tiles, d_ref, ref_start, ref_len,
+            hipLaunchKernelGGL(call_tiles_wave_kernel<1>, dim3((unsigned)n_tiles), dim3(64), 0, s, d_tuples, d_tiles, n_tiles, d_ref, ref_start, ref_len,
                                d_records, d_tr, h->P, (const DeviceParams*)h->d_params.p);
         else if (!two)
-            hipExtLaunchKernelGGL(call_tiles_wave_kernel<1>, dim3((unsigned)n_tiles), dim3(64), lds, s, e0, e1, 0u, d_tuples, d_tiles,
+            hipExtLaunchKernelGGL(call_tiles_wave_kernel<1>, dim3((unsigned)n_tiles), dim3(64), 0, s, e0, e1, 0u, d_tuples, d_tiles,
                                   n_tiles, d_ref, ref_start, ref_len, d_records, d_tr, h->P, (const DeviceParams*)h->d_params.p);
         else if (!e0 && !e1)
-            hipLaunchKernelGGL(call_tiles_wave_kernel<2>, dim3((unsigned)n_tiles), dim3(128), lds, s, d_tuples, d_tiles, n_tiles, d_ref, ref_start, ref_len,
+            hipLaunchKernelGGL(call_tiles_wave_kernel<2>, dim3((unsigned)n_tiles), dim3(128), 0, s, d_tuples, d_tiles, n_tiles, d_ref, ref_start, ref_len,
                                d_records, d_tr, h->P, (const DeviceParams*)h->d_params.p);
         else
-            hipExtLaunchKernelGGL(call_tiles_wave_kernel<2>, dim3((unsigned)n_tiles), dim3(128), lds, s, e0, e1, 0u, d_tuples, d_tiles,
+            hipExtLaunchKernelGGL(call_tiles_wave_kernel<2>, dim3((unsigned)n_tiles), dim3(128), 0, s, e0, e1, 0u, d_tuples, d_tiles,
                                   n_tiles, d_ref, ref_start, ref_len, d_records, d_tr, h->P, (const DeviceParams*)h->d_params.p);
         return hipSuccess;
     }
-    hipExtLaunchKernelGGL(call_tiles_kernel, dim3((unsigned)n_tiles), dim3(kBlock), lds, s, e0, e1, 0u, d_tuples, d_tiles, n_tiles, d_ref,
+    hipExtLaunchKernelGGL(call_tiles_kernel, dim3((unsigned)n_tiles), dim3(kBlock), 0, s, e0, e1, 0u, d_tuples, d_tiles, n_tiles, d_ref,
                           ref_start, ref_len, d_records, d_tr, h->P);
     return hipSuccess;
 }

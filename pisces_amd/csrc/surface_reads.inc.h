@@ -386,17 +386,11 @@ static int32_t launch_found_scan(PiscesHip* h, int32_t* a, int32_t* b, int32_t n
     hipLaunchKernelGGL(scan_apply_kernel, dim3((unsigned)n_blocks), dim3(1024), 0, h->stream, a, b, n, (const long long*)h->d_scan_sums.p, n_blocks);
     return PISCES_OK;
 }
-// the count / emit passes of the candidate walk: a wave per read when the M operations are walked (finder_kernels.hip.h, the wave form),
-// a lane per read otherwise (insertions and deletions only: a read is a loop over its CIGAR) or when PISCES_HIP_FINDER=lane asks for it
+// the count / emit passes of the candidate walk, a lane per read: the M operations walked events first (finder_kernels.hip.h) up to
+// minBQ 127, base by base above it or when PISCES_HIP_FINDER=bases asks for it; insertions and deletions only when no M operation is walked
 static void launch_find_count(PiscesHip* h, const DevReadBatch& db, const uint8_t* d_deldirs, const FinderParams& FP, int32_t nr, int32_t* n_found, int32_t* n_pool)
 {
-    if (FP.snvs_and_mnvs && h->finder_wave == 2) {
-        hipLaunchKernelGGL(find_batch_wave_kernel<false>, dim3((unsigned)((nr + 255) / 256)), dim3(256), 0, h->stream, db, d_deldirs, (const uint8_t*)h->d_ref.p, h->ref_len, FP,
-                           n_found, n_pool, (const int32_t*)nullptr, (const int32_t*)nullptr, (DevFound*)nullptr, (uint8_t*)nullptr, (unsigned int*)nullptr, 0, (int32_t*)nullptr);
-    } else if (FP.snvs_and_mnvs && h->finder_wave) {
-        const unsigned waves = (unsigned)((nr + kReadsPerWave - 1) / kReadsPerWave);
-        hipLaunchKernelGGL(find_count_wave_kernel, dim3((waves + 3) / 4), dim3(256), 0, h->stream, db, d_deldirs, (const uint8_t*)h->d_ref.p, h->ref_len, FP, n_found, n_pool);
-    } else if (FP.snvs_and_mnvs && h->finder_wave != 3 && FP.min_bq <= 127) {
+    if (FP.snvs_and_mnvs && !h->finder_bases && FP.min_bq <= 127) {
         hipLaunchKernelGGL(find_count_kernel<true>, dim3((unsigned)((nr + 255) / 256)), dim3(256), 0, h->stream, db, d_deldirs, (const uint8_t*)h->d_ref.p, h->ref_len, FP, n_found, n_pool);
     } else {
         hipLaunchKernelGGL(find_count_kernel<false>, dim3((unsigned)((nr + 255) / 256)), dim3(256), 0, h->stream, db, d_deldirs, (const uint8_t*)h->d_ref.p, h->ref_len, FP, n_found, n_pool);
@@ -405,14 +399,7 @@ static void launch_find_count(PiscesHip* h, const DevReadBatch& db, const uint8_
 static void launch_find_emit(PiscesHip* h, const DevReadBatch& db, const uint8_t* d_deldirs, const FinderParams& FP, int32_t nr, const int32_t* d_slots,
                              const int32_t* d_pool_first, DevFound* out, uint8_t* pool, unsigned int* misc, int32_t pool_capacity)
 {
-    if (FP.snvs_and_mnvs && h->finder_wave == 2) {
-        hipLaunchKernelGGL(find_batch_wave_kernel<true>, dim3((unsigned)((nr + 255) / 256)), dim3(256), 0, h->stream, db, d_deldirs, (const uint8_t*)h->d_ref.p, h->ref_len, FP,
-                           (int32_t*)nullptr, (int32_t*)nullptr, d_slots, d_pool_first, out, pool, misc, pool_capacity, (int32_t*)(misc + 1));
-    } else if (FP.snvs_and_mnvs && h->finder_wave) {
-        const unsigned waves = (unsigned)((nr + kReadsPerWave - 1) / kReadsPerWave);
-        hipLaunchKernelGGL(find_emit_wave_kernel, dim3((waves + 3) / 4), dim3(256), 0, h->stream, db, d_deldirs, (const uint8_t*)h->d_ref.p, h->ref_len, FP, d_slots,
-                           d_pool_first, out, pool, misc, pool_capacity, (int32_t*)(misc + 1));
-    } else if (FP.snvs_and_mnvs && h->finder_wave != 3 && FP.min_bq <= 127) {
+    if (FP.snvs_and_mnvs && !h->finder_bases && FP.min_bq <= 127) {
         hipLaunchKernelGGL(find_emit_kernel<true>, dim3((unsigned)((nr + 255) / 256)), dim3(256), 0, h->stream, db, d_deldirs, (const uint8_t*)h->d_ref.p, h->ref_len, FP, d_slots,
                            d_pool_first, out, pool, misc, pool_capacity, (int32_t*)(misc + 1));
     } else {

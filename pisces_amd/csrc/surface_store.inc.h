@@ -494,16 +494,7 @@ static int32_t store_device_checks(PiscesHip* h, uint8_t* d, const StageLayout& 
     const bool stream = n_seq > 0 && (src || F.d_codes || has_dirs);
     // (four sixteen-byte pieces of each array a lane a trip — add_fused_kernel's kStreamPieces — and every lane the same number of trips)
     F.stream_blocks = stream ? (int32_t)std::min<int64_t>(((int64_t)n_seq + 4 * 16 * 256 - 1) / (4 * 16 * 256), 16384) : 0;
-    // PISCES_HIP_STREAM_WGS_PER_CU = k > 0: at most k x CUs persistent stream workgroups, in FRONT of the read workgroups (add_fused_kernel)
-    F.stream_first = 0;
-    if (h->stream_wgs_per_cu > 0 && F.stream_blocks > 0) {
-        F.stream_blocks = (int32_t)std::min<int64_t>(F.stream_blocks, (int64_t)h->stream_wgs_per_cu * h->n_cus);
-        F.stream_first = 1;
-    }
     F.misc_blocks = src ? (int32_t)std::min<int64_t>(std::max<int64_t>((misc_bytes / 16 + 255) / 256, 1), 64) : 0;
-    // (1: the read workgroups in front.  Measured, XCD-aware, on config 2's batch: every 2nd / 3rd / 4th / 8th unit of eight workgroups a read
-    // unit: 96 / 95 / 115 / 106 us against 83 with the read role in front; PISCES_HIP_ROLE_STRIDE for the A / B)
-    F.role_stride = std::max<int32_t>(1, std::min<int32_t>(h->role_stride, (F.read_blocks + F.stream_blocks + F.misc_blocks) / std::max((F.read_blocks + 7) / 8 * 8, 1)));
     F.scan_state = h->d_fused_scan.p;
     F.done = (unsigned int*)(h->d_fused_words.p + kWordsDone);
     F.totals = (long long*)(h->d_fused_words.p + kWordsTotals);
@@ -964,22 +955,16 @@ static hipError_t launch_call_store_tiles(PiscesHip* h, hipStream_t s, const uin
     if (nw == 0) nw = h->kernel_variant == 2 ? 1 : h->kernel_variant == 3 ? 2 : (int64_t)n_tiles <= (int64_t)h->n_cus ? 16 /* (a tile a CU at most: all sixteen waves; 235 tiles at 5000x: 69 us against 74 with eight) */
                       : (int64_t)n_tiles * 4 <= (int64_t)h->n_cus * 12 ? 4 : (int64_t)n_tiles <= (int64_t)h->n_cus * 32 ? 2 : 1;
     // several tiles a CU (store_kernels.hip.h): the workgroups trade tiles by price inside small groups (the default), or take them in
-    // tile_order_kernel's order (PISCES_HIP_TILE_ORDER=1: a launch in front), or in position order (=0)
-    const int32_t* order = nullptr;
+    // position order (PISCES_HIP_TILE_ORDER=0)
     int32_t trade_cus = 0;
     // (from 4 to 8 tiles a CU: beyond, the CUs' shares even out by themselves and the trade's pricing only delays a tile's start —
     // 3 200 / 4 688 / 9 376 tiles: 60.3 / 48.3 / 92.3 us in position order, 61.0 / 49.2 / 93.0 traded, profiles/r05_tile_order.txt)
-    if (h->tile_order == 2 && nw <= 2 && (int64_t)n_tiles >= 4 * (int64_t)h->n_cus && (int64_t)n_tiles <= 8 * (int64_t)h->n_cus && h->n_cus >= 8)
+    if (h->trade_tiles && nw <= 2 && (int64_t)n_tiles >= 4 * (int64_t)h->n_cus && (int64_t)n_tiles <= 8 * (int64_t)h->n_cus && h->n_cus >= 8)
         trade_cus = (int32_t)(h->n_cus / 8);
-    if (h->tile_order == 1 && nw <= 2 && (int64_t)n_tiles >= 4 * (int64_t)h->n_cus && h->n_cus >= 8) {
-        if (h->d_tile_order.reserve((size_t)n_tiles) != hipSuccess) return hipErrorOutOfMemory;
-        hipLaunchKernelGGL(tile_order_kernel, dim3(8), dim3(256), 0, s, V, d_tiles, R, n_tiles, (int32_t)(h->n_cus / 8), h->d_tile_order.p);
-        order = h->d_tile_order.p;
-    }
     // issue priority for walking waves: launches whose workgroups are all resident at once (8 tiles a CU at two waves a tile)
-    const int32_t walk_prio = (h->store_prio && nw == 2 && (int64_t)n_tiles <= 8 * (int64_t)h->n_cus) ? 1 : 0;
+    const int32_t walk_prio = (nw == 2 && (int64_t)n_tiles <= 8 * (int64_t)h->n_cus) ? 1 : 0;
 #define PISCES_LAUNCH_STORE(NW)                                                                                                                     \
-    hipExtLaunchKernelGGL(call_store_tiles_kernel<NW>, dim3((unsigned)n_tiles), dim3(64 * NW), 0u, s, e0, e1, 0u, V, d_tuples, d_tiles, R, n_tiles, order, trade_cus, walk_prio, d_ref, \
+    hipExtLaunchKernelGGL(call_store_tiles_kernel<NW>, dim3((unsigned)n_tiles), dim3(64 * NW), 0u, s, e0, e1, 0u, V, d_tuples, d_tiles, R, n_tiles, trade_cus, walk_prio, d_ref, \
                           ref_start, ref_len, d_records, d_tr, h->P, (const DeviceParams*)h->d_params.p)
     if (nw >= 16) PISCES_LAUNCH_STORE(16);
     else if (nw >= 8) PISCES_LAUNCH_STORE(8);

@@ -16,7 +16,6 @@ from tests import orc
 FORMS = [("rows merged by copy", dict(PISCES_HIP_MERGE_IN_PLACE=0), "host"), ("checks on the device", dict(PISCES_HIP_DEVICE_CHECKS=1), "host"),
          ("checks on the host", dict(PISCES_HIP_DEVICE_CHECKS=0), "host"), ("candidates merged on the host", dict(PISCES_HIP_DEVICE_MERGE=0), "host"),
          ("candidates merged on the device", dict(PISCES_HIP_DEVICE_MERGE=1), "host"), ("walk base by base", dict(PISCES_HIP_FINDER="bases"), "host"),
-         ("walk a wave a read", dict(PISCES_HIP_FINDER="wave"), "host"), ("walk in batches", dict(PISCES_HIP_FINDER="batch"), "host"),
          ("genotypes by the host pass", dict(PISCES_HIP_DEVICE_GENOTYPER=0), "host"), ("every batch its own segment", dict(PISCES_HIP_STORE_DIRECT_BYTES=0), "host"),
          ("every batch appended", dict(PISCES_HIP_STORE_DIRECT_BYTES=1 << 40, PISCES_HIP_STORE_SEAL_BYTES=1 << 40), "host"),
          ("reads in device memory", {}, "device"), ("candidates looked at after every add", {}, "peek"),

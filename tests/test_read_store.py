@@ -305,8 +305,8 @@ def test_thresholds_the_fused_kernel_is_not_compiled_for(torch_cuda):
                               "1360_tiles_groups_of_3_and_cus_left_over", "1792_tiles_no_cu_with_a_tile_more"])
 def test_whichever_tile_a_workgroup_takes_the_records_are_the_same(torch_cuda, n_loci, depth):
     """A launch of several tiles a CU deals its tiles by price (store_kernels.hip.h: exchanged_tile inside call_store_tiles_kernel, the
-    default; tile_order_kernel in front of it, PISCES_HIP_TILE_ORDER=1): every tile must be taken exactly once, so the records of one
-    flush are the bytes of the launch in position order (PISCES_HIP_TILE_ORDER=0).  Sizes: some CUs with one tile more than the
+    default): every tile must be taken exactly once, so the records of one flush are the bytes of the launch in position order
+    (PISCES_HIP_TILE_ORDER=0).  Sizes: some CUs with one tile more than the
     others (1 600 and 1 120 tiles on 256 CUs: groups of four) and none (2 048, 1 792: groups of four, rotated); 2 / 16 / 10 of an XCD's 32
     CUs with a tile more (1 040 / 1 920 / 1 360 tiles: groups of eight / two / three, the last with CUs that belong to no group)."""
     from pisces_amd import engine, synth
@@ -315,23 +315,21 @@ def test_whichever_tile_a_workgroup_takes_the_records_are_the_same(torch_cuda, n
     cfg = _abi.default_config()
     whole = synth.reads_of(p, p.base.shape[0], first_amplicon=0)
     out = {}
-    for order in ("0", "1", "2"):
+    for order in ("0", None):
         with env(PISCES_HIP_TILE_ORDER=order):
             with engine.HipVariantCaller(cfg) as c:
                 c.SetReference(ref)
                 c.AddAlleleCounts(whole)
                 out[order] = c.Call(None, capacity=2 * n_loci)
     assert len(out["0"]) >= n_loci
-    assert out["1"].tobytes() == out["0"].tobytes()
-    assert out["2"].tobytes() == out["0"].tobytes()
+    assert out[None].tobytes() == out["0"].tobytes()
 
 
 def test_tiles_of_any_size_and_switches_of_the_add_give_the_same_records(torch_cuda):
     """The tiles of a flush over whole blocks are described by value (RegularTiles) and may be of any size up to 64
     (PISCES_HIP_TILE_LOCI: 59 -> 17 tiles a block, 48 -> 21, 33 -> 31; the default 64 -> 16): a tile's records depend on its loci only, so
-    the compacted rows of the flush are the same bytes.  The same for the switches round 6 added to the add of a batch in device memory:
-    the position grid enqueued by the add itself (PISCES_HIP_DEFER_GRID=0) and the read role spread between the streaming workgroups
-    (PISCES_HIP_ROLE_STRIDE=3)."""
+    the compacted rows of the flush are the same bytes.  The same for the switch round 6 added to the add of a batch in device memory:
+    the position grid enqueued by the add itself (PISCES_HIP_DEFER_GRID=0)."""
     from pisces_amd import engine, synth
     p = synth.make_pileup(n_loci=40_000, depth=80, seed=17, device="cuda", with_tuples=False)
     ref = p.ref.cpu().numpy()
@@ -340,7 +338,7 @@ def test_tiles_of_any_size_and_switches_of_the_add_give_the_same_records(torch_c
     d = engine.DeviceReadBatch.from_host(whole, "cuda:0")
     out = {}
     for label, kw in (("default", {}), ("59", dict(PISCES_HIP_TILE_LOCI="59")), ("48", dict(PISCES_HIP_TILE_LOCI="48")), ("33", dict(PISCES_HIP_TILE_LOCI="33")),
-                      ("grid_in_the_add", dict(PISCES_HIP_DEFER_GRID="0")), ("stride_3", dict(PISCES_HIP_ROLE_STRIDE="3"))):
+                      ("grid_in_the_add", dict(PISCES_HIP_DEFER_GRID="0"))):
         with env(**kw):
             with engine.HipVariantCaller(cfg) as c:
                 c.SetReference(ref)
@@ -773,13 +771,12 @@ def test_candidate_rows_merged_in_place_equal_the_rows_merged_by_copy(torch_cuda
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("form", ["events", "bases", "wave", "batch"])
+@pytest.mark.parametrize("form", ["events", "bases"])
 def test_every_form_of_the_candidate_walk_equals_the_host_walk(torch_cuda, form):
     """ICandidateVariantFinder.FindCandidates (CandidateVariantFinder.cs:31-203) in the forms finder_kernels.hip.h holds — a lane a read
-    with the events first (the default), a lane a read base by base, a wave a read, a wave for 64 reads (PISCES_HIP_FINDER) — against the
-    host's base-by-base walk (pisces_hip_find_candidates, finder_walk.h): reads with any CIGAR, N bases, bytes that are no bases, low
-    qualities, qualities above 127, M operations shorter than a word and longer than a chunk of 64 bases, MNV limits from 1 to 6 bases
-    and gaps from 0 to 3."""
+    with the events first (the default) and a lane a read base by base (PISCES_HIP_FINDER=bases) — against the host's base-by-base walk
+    (pisces_hip_find_candidates, finder_walk.h): reads with any CIGAR, N bases, bytes that are no bases, low qualities, qualities above
+    127, M operations shorter than a word and longer than a chunk of 64 bases, MNV limits from 1 to 6 bases and gaps from 0 to 3."""
     from pisces_amd import engine
     rng = np.random.default_rng(77)
     ref = bytes(rng.choice(list(b"ACGTN"), 3000, p=[.245, .245, .245, .245, .02]).astype(np.uint8))
