@@ -361,23 +361,40 @@ struct PiscesHip {
     std::vector<std::pair<int32_t, int32_t>> intervals;   // sorted, disjoint [start, end]
     int32_t own_lo = 1, own_hi = 0x7FFFFFFF;              // pisces_hip_set_owned_range
     int64_t stats[4] = {0, 0, 0, 0};      // called, collapsed, reads processed, reads skipped
-    bool in_flush_begin = false;
     double prof[24] = {0};                 // development (PISCES_HIP_HOST_PROFILE=1): host seconds by phase of a flush, printed when the handle goes
     bool prof_on = false;
     int64_t pcie[4] = {0, 0, 0, 0};          // pisces_hip_transfer_bytes: H2D reads / file bytes, D2H records, D2H candidate records, D2H counts
     double host_time[4] = {0, 0, 0, 0};   // pisces_hip_host_time: seconds in add_reads, in flush, of that waiting for the device; flushes
 
-    // cached result of a flush that did not fit the caller's buffer
-    bool pending_valid = false;
-    int32_t pending_up_to = 0;
-    std::vector<PiscesCalledAllele> pending;
-    std::vector<int32_t> pending_cand_index;        // per record: index into pending_cands, -1 for Reference / SNV rows
-    std::vector<HostCandidate> pending_cands;       // called insertion / deletion candidates (their allele strings)
-    std::vector<int32_t> pending_keys;
-    int64_t pending_called = 0;
-    bool pending_dropped = false;            // the flushed blocks' log entries are already gone from the other log buffer (kept entries there)
-    unsigned long long pending_kept = 0;
-    int64_t pending_collapsed = 0;
+    // A flush's result from flush_build until the caller has taken it (every pisces_hip_flush* entry hands it out), then until the next
+    // flush for the views.  valid: the batch is made but not committed — a flush that reported PISCES_E_BUFFER_TOO_SMALL keeps it for the
+    // call that repeats it with the same upTo.
+    struct FlushResult {
+        bool valid = false;
+        int32_t up_to = 0;
+        PiscesCalledAllele* view = nullptr;    // the rows where the last kernel left them (the pinned download buffer, h_dl), else `rows`
+        size_t n_view = 0;
+        std::vector<PiscesCalledAllele> rows;
+        std::vector<int32_t> index;            // per row: index into cands, -1 for Reference / SNV rows (empty: a batch the device called alone)
+        std::vector<HostCandidate> cands;      // the called insertion / deletion / MNV candidates (their allele strings)
+        std::vector<PiscesCandidate> exported; // cands and their allele strings as the views hand them out
+        std::vector<uint8_t> alleles;
+        std::vector<int32_t> keys;             // the flushed blocks
+        int64_t called = 0, collapsed = 0;
+        bool dropped = false;                  // the flushed blocks' log entries are already gone from the other log buffer (kept entries there)
+        unsigned long long kept = 0;
+        const PiscesCalledAllele* data() const { return view ? view : rows.data(); }
+        size_t size() const { return view ? n_view : rows.size(); }
+        void clear()
+        {
+            valid = dropped = false;
+            view = nullptr;
+            n_view = 0;
+            rows.clear(); index.clear(); cands.clear(); exported.clear(); alleles.clear(); keys.clear();
+            called = collapsed = 0;
+            kept = 0;
+        }
+    } result;
 
     // observation log on the device: (position, tuple) of every allele-count increment of the blocks not yet flushed,
     // appended by expand_reads_kernel / pisces_hip_add_observations, bucketed by tile at flush time
@@ -400,7 +417,6 @@ struct PiscesHip {
     } stage[2];
     int stage_cur = 0;
     uint8_t* h_stage = nullptr;              // = stage[stage_cur].h after stage_reserve
-    DeviceBuf<uint8_t> d_stage_alias;        // unused placeholder (kept empty)
     DeviceBuf<int32_t> d_bucket;             // BucketMap tables
     std::vector<int32_t> bucket_host[4];
     int bucket_host_next = 0;
@@ -415,28 +431,10 @@ struct PiscesHip {
         int32_t* hdr = nullptr;                // {records, called, kept (8 bytes)} in the pinned download buffer
         PiscesCalledAllele* hrec = nullptr;
         size_t spec = 0;                       // records that come back with the header; more only with a second copy
-        const PiscesCalledAllele* data = nullptr;   // state 2: the results
-        size_t n = 0;
-        std::vector<PiscesCalledAllele> owned; // state 2, when the flush had to run synchronously (host-side candidates, genotypers, ...)
-        std::vector<int32_t> owned_index;      // ... and what pisces_hip_flush_ex returns beside the records (pisces_hip_flush_end_ex)
-        std::vector<PiscesCandidate> owned_cands;
-        std::vector<uint8_t> owned_alleles;
-        size_t n_cands = 0, n_allele_bytes = 0;
-    } async;
-    struct FlushView {                        // pisces_hip_flush_view: what the last flush handed out in place
-        bool wanted = false;
-        const PiscesCalledAllele* data = nullptr;
-        size_t n = 0;
-        std::vector<PiscesCalledAllele> rows;  // the merged rows of a batch with host-side candidates (otherwise data points into h_dl)
-        std::vector<int32_t> index;
-        std::vector<PiscesCandidate> cands;
-        std::vector<uint8_t> alleles;
-    } view;
+    } async;                                 // (state 2: the results are in `result`)
     int64_t log_known_holes = 0;             // slots of the log that the last asynchronous drop left as holes (0 after any other drop)
     size_t staged_total = 0;                 // bytes pisces_hip_stage_reads laid out in the current staging buffer (0: nothing staged)
     uint8_t* h_dl = nullptr;                 // pinned download buffer of flush
-    const PiscesCalledAllele* pending_view = nullptr;   // the pending records when they are the download buffer's as they came (no host-side
-    size_t pending_view_n = 0;                          // candidates, genotyper or forced alleles to merge in): no copy into `pending`
     // pinned arena of the small uploads of a flush (bucket tables, tile geometry, gapped-MNV counts): a copy from pageable memory makes
     // the host wait until the stream has caught up, i.e. it serialises the flush's enqueueing with the device; from pinned memory it is
     // asynchronous.  Bump-allocated, rewound when the stream is known to be idle (every flush ends with a synchronisation).
@@ -627,11 +625,9 @@ static int32_t consume_found(PiscesHip* h);
 // A flush that reported PISCES_E_BUFFER_TOO_SMALL has made its batch (collapsed candidates, MNV leftovers handed to later blocks, ...)
 // and keeps it until the caller repeats the call with buffers that hold it.  Until then the state must not move: every entry that
 // would change it refuses.
-static int32_t refuse_while_batch_is_open(PiscesHip* h, const char* what);
-
 static int32_t refuse_while_batch_is_open(PiscesHip* h, const char* what)
 {
-    if (!h->pending_valid) return PISCES_OK;
+    if (!h->result.valid) return PISCES_OK;
     return fail(h, PISCES_E_STATE, std::string(what) + ": a flush reported PISCES_E_BUFFER_TOO_SMALL; repeat it with larger buffers first");
 }
 

@@ -1,6 +1,6 @@
 // surface_flush.inc.h — part of pisces_hip.hip (included there, inside its extern "C" block; not a translation unit of its own).
 // IAlleleCaller.Call behind the C ABI: tile geometry and bucketing of the observation log, DoneProcessing's log compaction, the device
-// calls of a batch (call_blocks), VariantCollapser / MnvReallocator / the candidate kernel (call_spanning), pisces_hip_flush[_ex] with the
+// calls of a batch (call_blocks_enqueue), VariantCollapser / MnvReallocator / the candidate kernel (call_spanning), the flush as stages (flush_build) with the
 // block schedule, and the IAlleleSource read-backs (counts, base-quality sums, gapped-MNV reference counts, candidates, statistics).
 
 // Builds tiles + tile-bucketed tuples for a set of blocks. Tiles follow the 1000-locus block grid
@@ -338,8 +338,6 @@ static int32_t call_blocks_enqueue(PiscesHip* h, const std::vector<int32_t>& key
 {
     *st = CallBlocksInFlight();
     h->fold.valid = false;
-    h->pending_view = nullptr;
-    h->pending_view_n = 0;
     if (keys.empty()) return PISCES_OK;
     if (!h->d_ref.p) return fail(h, PISCES_E_STATE, "flush: set_reference has not been called");
     const bool window = h->cfg.noise_model == PISCES_NOISE_WINDOW;
@@ -538,31 +536,6 @@ static void dump_tile_stamps(PiscesHip* h)
     if (FILE* fp = fopen(path, "wb")) { fwrite(tr.data(), sizeof(PiscesCalledAllele), tr.size(), fp); fclose(fp); }
 }
 #endif
-// device work of one flush: returns called alleles of `keys` sorted by (position, ref, alt)
-// as_view: the records are not copied into `out`; h->pending_view points at them in the pinned download buffer (valid until the next
-// call_blocks)
-static int32_t call_blocks(PiscesHip* h, const std::vector<int32_t>& keys, std::vector<PiscesCalledAllele>& out, int64_t* n_called,
-                           bool with_drop = false, bool* dropped = nullptr, unsigned long long* kept = nullptr, bool as_view = false, bool genotype_on_device = false)
-{
-    out.clear();   // (*n_called accumulates: the caller zeroes it)
-    if (dropped) *dropped = false;
-    CallBlocksInFlight st;
-    int32_t rc = call_blocks_enqueue(h, keys, with_drop, -1, &st, false, genotype_on_device);
-    if (rc || !st.active) return rc;
-    PISCES_TIMED_WAIT(h, hipStreamSynchronize(h->stream));
-    h->h_meta_used = 0;   // the stream is idle: nothing reads the arena any more
-#ifdef PISCES_STORE_TIMING
-    dump_tile_stamps(h);
-#endif
-    int32_t total = 0;
-    rc = call_blocks_finish(h, st, &total, n_called, kept);
-    if (rc) return rc;
-    if (st.drop_now && dropped) *dropped = true;
-    if (as_view) { h->pending_view = st.hrec; h->pending_view_n = (size_t)total; }
-    else out.assign(st.hrec, st.hrec + total);
-    return PISCES_OK;
-}
-
 // ------------------------------------------------------------------------------------------------
 // VariantCollapser.Collapse (exe/Pisces/Logic/VariantCalling/VariantCollapser.cs:31-79) for the host-side candidates of a batch:
 // insertions / deletions, and with MNV calling on the SNV / MNV candidates too.  With it off SNV candidates need no pass here: an
@@ -1090,36 +1063,155 @@ static int32_t split_prepare(PiscesHip* h, const std::vector<int32_t>& keys, int
     return PISCES_OK;
 }
 
-// IAlleleCaller.Call for the host-found candidates of `keys` (AlleleCaller.CallForPositions :60-141): anchor-resolved counts of every
-// block a candidate touches -> collapser -> call_spanning_kernel -> callable candidates with their records.  With MNV calling on
-// the candidates include the SNVs / MNVs of the read walk: MNV candidates are processed first, the ones that are not callable go
-// through MnvReallocator on the host, leftovers past the last cleared block return to the state as candidates of the next block,
-// reference support taken by gapped MNVs is registered (it reaches the Reference records through call_blocks, which runs after
-// this), and every callable allele is processed again.  ref_overrides: Reference alleles that reallocation added support to
-// (they replace the tile kernels' Reference record of that position).
-// blocks_first: the tile kernels of this flush are enqueued already (their Reference records do not know the reference support that
-// gapped MNVs of THIS batch take: the Reference alleles of those positions come from here, as overrides), and h->fold says where their
-// folded counts lie.
-static int32_t call_spanning(PiscesHip* h, const std::vector<int32_t>& keys, int32_t up_to_position, std::vector<PiscesCalledAllele>& recs,
-                             std::vector<HostCandidate>& called, int64_t* n_called, int64_t* n_collapsed,
-                             std::vector<PiscesCalledAllele>& ref_overrides, bool blocks_first = false)
+// What the stages of call_spanning share: the batch's candidates, the loci whose counts they read and where those counts lie.
+struct SpanBatch {
+    PiscesHip* h;
+    const std::vector<int32_t>* keys;        // the cleared blocks (ascending)
+    int32_t up_to_position;
+    bool blocks_first;
+    std::vector<HostCandidate> work;         // a copy: the blocks keep their candidates until DoneProcessing
+    int32_t max_cleared = -1;                // >= 0: candidates of held blocks joined the batch (AddCollapsableFromOtherBlocks)
+    std::vector<BlockObs::Unwalked> unw;     // MNV calling off: bases of X / = operations no SNV candidate stands for, by (position, base)
+    // where the candidates' counts lie: the folded counts of the tile kernels' launch, or the tensor over `tiles`
+    bool fold_ok = false, sparse_tiles = false;
+    std::vector<PiscesTile> tiles;
+    std::vector<int32_t> bkeys, tile_starts;   // the tensor's blocks (observation log) / 64-locus tiles (read store)
+    const int32_t* d_folded = nullptr;
+    bool counts_missing = false;
+    // the gathered count rows the host reads (collapser frequencies, reallocator, SNV support)
+    const int32_t* host_counts = nullptr;
+    bool rows_missing = false;
+    // the last device pass: records + IsCallable
+    std::vector<PiscesCalledAllele> raw;
+    std::vector<uint8_t> callable;
+    bool second_pass = false;                // MNV mode: the pass over every callable allele, after the MNV-only pass
+    // the MNV pass and the reallocator
+    MnvArena arena;
+    std::vector<CandPtr> callable_alleles;   // AlleleCaller's callableAlleles (non-Reference ones and touched Reference ones)
+    std::map<int32_t, CandPtr> touched_refs; // Reference candidates created for the reallocator, by position
+    std::vector<CandPtr> failed;
+    std::vector<const HostCandidate*> final_list;
+};
+
+static int span_atype(char ch) { return ch == 'A' ? 0 : ch == 'G' ? 1 : ch == 'C' ? 2 : ch == 'T' ? 3 : 4; }
+static bool in_batch(const SpanBatch& B, int32_t p) { return std::binary_search(B.keys->begin(), B.keys->end(), block_key(B.h, p)); }
+
+// start / end points (CoverageCalculator.Compute :27-41)
+static void span_endpoints(const HostCandidate& c, int32_t& sp, int32_t& ep)
 {
-    recs.clear();
-    called.clear();
-    ref_overrides.clear();
-    *n_collapsed = 0;
-    const bool mnv_mode = h->cfg.call_mnvs != 0;
-    const bool window = h->cfg.noise_model == PISCES_NOISE_WINDOW;
-    std::unique_ptr<HostTimer> prof(new HostTimer(h->prof_on ? &h->prof[1] : nullptr));
-    auto phase = [&](int i) { prof.reset(); prof.reset(new HostTimer(h->prof_on ? &h->prof[i] : nullptr)); };
-    std::vector<HostCandidate> work;   // a copy: the blocks keep their candidates until DoneProcessing
+    if (c.category == PISCES_CAT_DELETION) { sp = c.position + 1; ep = c.position + (int32_t)c.ref.size() - 1; }
+    else if (c.category == PISCES_CAT_MNV) { sp = c.position; ep = c.position + (int32_t)c.alt.size() - 1; }
+    else if (c.category == PISCES_CAT_INSERTION) { sp = c.position; ep = c.position + 1; }
+    else { sp = c.position; ep = c.position; }
+}
+
+static int32_t unwalked_of(const SpanBatch& B, int32_t position, char alt, int d)
+{
+    auto it = std::lower_bound(B.unw.begin(), B.unw.end(), std::make_pair(position, (uint8_t)alt), [](const BlockObs::Unwalked& u, const std::pair<int32_t, uint8_t>& k) {
+        return u.position != k.first ? u.position < k.first : u.alt < k.second; });
+    return (it != B.unw.end() && it->position == position && it->alt == (uint8_t)alt) ? it->sup[d] : 0;
+}
+
+static bool in_fold(const SpanBatch& B, int32_t p) { return B.fold_ok && p >= B.h->fold.lo && p <= B.h->fold.hi; }
+static int32_t tile_start_of(const SpanBatch& B, int32_t p)
+{
+    const int bs = B.h->cfg.block_size;
+    const int32_t b0 = (block_key(B.h, p) - 1) * bs + 1;
+    return b0 + ((p - b0) / kTile) * kTile;
+}
+
+// the locus' place in the counts: >= 0 the tensor, <= -2 the folded counts, -1 none
+static int64_t locus_index(SpanBatch& B, int32_t p, bool may_fold = true)
+{
+    PiscesHip* h = B.h;
+    if (p <= 0) return -1;
+    if (may_fold && in_fold(B, p)) return -((int64_t)(p - h->fold.lo) + 2);   // the folded counts of the tile kernels' launch
+    const int32_t k = block_key(h, p);
+    if (!h->blocks.count(k)) return -1;   // no block: no counts (RegionStateManager.cs:222-226)
+    if (B.sparse_tiles) {
+        const int32_t ts = tile_start_of(B, p);
+        auto it = std::lower_bound(B.tile_starts.begin(), B.tile_starts.end(), ts);
+        if (it == B.tile_starts.end() || *it != ts) { B.counts_missing = true; return -1; }
+        return (int64_t)(it - B.tile_starts.begin()) * kTile + (p - ts);
+    }
+    const int bs = h->cfg.block_size;
+    const int tiles_per_block = (bs + kTile - 1) / kTile;
+    auto it = std::lower_bound(B.bkeys.begin(), B.bkeys.end(), k);
+    if (it == B.bkeys.end() || *it != k) { B.counts_missing = true; return -1; }
+    const int64_t bi = it - B.bkeys.begin();
+    const int32_t off = p - ((k - 1) * bs + 1);
+    return (bi * tiles_per_block + off / kTile) * kTile + off % kTile;
+}
+
+// a locus index's row among the gathered count rows
+static int64_t row_index(SpanBatch& B, int64_t li)
+{
+    if (li == -1) return -1;
+    auto it = B.h->row_of_locus.find(li);
+    if (it == B.h->row_of_locus.end()) { B.rows_missing = true; return -1; }
+    return it->second;
+}
+
+// the reads of allele type `at` in direction d at a gathered row
+static int32_t row_count(const SpanBatch& B, int64_t row, int at, int d)
+{
+    const int32_t* r = B.host_counts + row * PISCES_COUNTS_PER_LOCUS + (at * 3 + d) * PISCES_NUM_ANCHORS;
+    int32_t n = 0;
+    for (int an = 0; an < PISCES_NUM_ANCHORS; an++) n += r[an];
+    return n;
+}
+
+static void to_dev(SpanBatch& B, const HostCandidate& c, DevCandidate& d)
+{
+    std::memset(&d, 0, sizeof(d));
+    d.position = c.position;
+    d.category = c.category;
+    d.ref_len = (int32_t)c.ref.size();
+    d.alt_len = (int32_t)c.alt.size();
+    for (int k = 0; k < 3; k++) { d.sup[k] = c.support_by_dir[k]; d.anch[k] = c.well_anchored_by_dir[k]; }
+    d.first_base = d.last_base = PISCES_ALLELE_N;
+    if (c.category == PISCES_CAT_INSERTION && c.alt.size() >= 2) {
+        d.first_base = span_atype(c.alt[1]);
+        d.last_base = span_atype(c.alt[c.alt.size() - 1]);
+    }
+    int32_t sp, ep;
+    span_endpoints(c, sp, ep);
+    const bool may_fold = c.category != PISCES_CAT_INSERTION;
+    d.start_idx = locus_index(B, sp, may_fold);
+    d.end_idx = locus_index(B, ep, may_fold);
+    d.gapped = 0;
+    if (c.category == PISCES_CAT_SNV || c.category == PISCES_CAT_REFERENCE) {
+        auto it = B.h->gapped_mnv_ref.find(c.position);
+        d.gapped = it == B.h->gapped_mnv_ref.end() ? 0 : it->second;
+    }
+}
+
+static bool owned(const PiscesHip* h, int32_t position) { return position >= h->own_lo && position <= h->own_hi; }   // (interval sharding: pisces_hip_set_owned_range)
+static bool inside_intervals(const PiscesHip* h, int32_t position)   // ShouldReport (AlleleCaller.cs:260-263)
+{
+    if (!owned(h, position)) return false;
+    if (h->intervals.empty()) return true;
+    auto it = std::lower_bound(h->intervals.begin(), h->intervals.end(), position,
+                               [](const std::pair<int32_t, int32_t>& iv, int32_t p) { return iv.second < p; });
+    return it != h->intervals.end() && it->first <= position;
+}
+
+// The batch's candidates (RegionState.GetAllCandidates walks _candidateVariantsLookup by position, each position in arrival order,
+// RegionState.cs:388-391), then AddCollapsableFromOtherBlocks (RegionStateManager.cs:321-324, 441-457): when an allele of the cleared blocks
+// reaches past the last cleared position and the collapser is on, the SNV / MNV candidates of the held blocks up to upTo that end at or before
+// upTo and are not open on the right (RegionState.ExtractCollapsable :470-490) leave their blocks and join this batch, where candidates of the
+// cleared blocks may collapse into them; whatever of them is left after collapsing goes back to the state (span_collapse)
+static void span_gather_candidates(SpanBatch& B)
+{
+    PiscesHip* h = B.h;
+    const std::vector<int32_t>& keys = *B.keys;
+    std::vector<HostCandidate>& work = B.work;
     {
         size_t total = 0;
         for (int32_t key : keys) total += h->blocks[key].cands.size();
         work.reserve(total);
     }
     for (int32_t key : keys) {
-        // RegionState.GetAllCandidates walks _candidateVariantsLookup by position, each position in arrival order (RegionState.cs:388-391)
         const size_t first = work.size();
         for (auto& c : h->blocks[key].cands) {
             // (split form of MNV calling: a fully anchored SNV of the read walk on a locus that is not dirty is the tile kernels' to call)
@@ -1163,543 +1255,485 @@ static int32_t call_spanning(PiscesHip* h, const std::vector<int32_t>& keys, int
         }
     }
     const int bs = h->cfg.block_size;
-    // AddCollapsableFromOtherBlocks (RegionStateManager.cs:321-324, 441-457): when an allele of the cleared blocks reaches past the last
-    // cleared position and the collapser is on, the SNV / MNV candidates of the held blocks up to upTo that end at or before upTo and are
-    // not open on the right (RegionState.ExtractCollapsable :470-490) leave their blocks and join this batch, where candidates of the
-    // cleared blocks may collapse into them; whatever of them is left after collapsing goes back to the state (below)
-    int32_t max_cleared = -1;
-    if (!keys.empty() && up_to_position >= 0 && h->cfg.collapse) {
-        int32_t max_endpoint = 0;
-        for (int32_t key : keys) max_endpoint = std::max(max_endpoint, h->blocks[key].max_allele_endpoint);
-        if (max_endpoint > keys.back() * bs) {
-            max_cleared = keys.back() * bs;
-            for (auto& kv : h->blocks) {   // ascending block order
-                const int32_t start = (kv.first - 1) * bs + 1;
-                if (start <= max_cleared || start > up_to_position) continue;
-                std::vector<HostCandidate> kept;
-                const size_t first = work.size();
-                for (auto& c : kv.second.cands) {
-                    const bool collapsable = (c.category == PISCES_CAT_MNV || c.category == PISCES_CAT_SNV) && !c.open_right &&
-                                             c.position + (int32_t)c.alt.size() - 1 <= up_to_position;
-                    (collapsable ? work : kept).push_back(c);
-                }
-                if (work.size() == first) continue;
-                std::stable_sort(work.begin() + (std::ptrdiff_t)first, work.end(), [](const HostCandidate& x, const HostCandidate& y) { return x.position < y.position; });
-                kv.second.cands.clear();   // (MaxAlleleEndpoint keeps its value: RegionState never lowers it)
-                kv.second.cand_index.clear();
-                kv.second.cand_next.clear();
-                for (auto& c : kept) add_candidate(h, c);
-            }
+    if (keys.empty() || B.up_to_position < 0 || !h->cfg.collapse) return;
+    int32_t max_endpoint = 0;
+    for (int32_t key : keys) max_endpoint = std::max(max_endpoint, h->blocks[key].max_allele_endpoint);
+    if (max_endpoint <= keys.back() * bs) return;
+    B.max_cleared = keys.back() * bs;
+    for (auto& kv : h->blocks) {   // ascending block order
+        const int32_t start = (kv.first - 1) * bs + 1;
+        if (start <= B.max_cleared || start > B.up_to_position) continue;
+        std::vector<HostCandidate> kept;
+        const size_t first = work.size();
+        for (auto& c : kv.second.cands) {
+            const bool collapsable = (c.category == PISCES_CAT_MNV || c.category == PISCES_CAT_SNV) && !c.open_right &&
+                                     c.position + (int32_t)c.alt.size() - 1 <= B.up_to_position;
+            (collapsable ? work : kept).push_back(c);
+        }
+        if (work.size() == first) continue;
+        std::stable_sort(work.begin() + (std::ptrdiff_t)first, work.end(), [](const HostCandidate& x, const HostCandidate& y) { return x.position < y.position; });
+        kv.second.cands.clear();   // (MaxAlleleEndpoint keeps its value: RegionState never lowers it)
+        kv.second.cand_index.clear();
+        kv.second.cand_next.clear();
+        for (auto& c : kept) add_candidate(h, c);
+    }
+}
+
+// MNV calling off: the bases of X / = operations on the batch's loci that the allele counts hold and no SNV candidate stands for
+// (ProcessCigarOps walks M operations only, CandidateVariantFinder.cs:44-71), by (position, read base).  The tile kernels leave the
+// variants of those loci alone (split_prepare made them dirty); their SNV candidates are made after the collapser (span_unwalked_snvs),
+// with the support the read walk's candidates have: the allele counts less these bases.
+static void span_gather_unwalked(SpanBatch& B)
+{
+    PiscesHip* h = B.h;
+    std::vector<BlockObs::Unwalked>& unw = B.unw;
+    for (int32_t key : *B.keys) {
+        const auto& u = h->blocks[key].unwalked;
+        unw.insert(unw.end(), u.begin(), u.end());
+    }
+    for (auto& c : B.work)   // an SNV candidate the host handed in: its locus is dirty; the other bases of the locus are made later, from the counts
+        if (c.category == PISCES_CAT_SNV && split_dirty_at(h, c.position) && c.alt.size() == 1 && in_batch(B, c.position))
+            unw.push_back({c.position, (uint8_t)c.alt[0], {0, 0, 0}});
+    if (B.max_cleared >= 0) {   // (SNV candidates of held blocks that joined the batch — forced ones: what the reads so far show at their positions)
+        std::vector<int32_t> seen;
+        for (auto& c : B.work) {
+            if (c.category != PISCES_CAT_SNV || c.position <= B.max_cleared || std::find(seen.begin(), seen.end(), c.position) != seen.end()) continue;
+            seen.push_back(c.position);
+            auto it = h->blocks.find(block_key(h, c.position));
+            if (it == h->blocks.end()) continue;
+            for (auto& u : it->second.unwalked)
+                if (u.position == c.position) unw.push_back(u);
         }
     }
-    // MNV calling off: the bases of X / = operations on the batch's loci that the allele counts hold and no SNV candidate stands for
-    // (ProcessCigarOps walks M operations only, CandidateVariantFinder.cs:44-71), by (position, read base).  The tile kernels leave the
-    // variants of those loci alone (split_prepare made them dirty); their SNV candidates are made here, after the collapser, with the
-    // support the read walk's candidates have: the allele counts less these bases.
-    std::vector<BlockObs::Unwalked> unw;
-    if (!h->snv_walk) {
-        for (int32_t key : keys) {
-            const auto& u = h->blocks[key].unwalked;
-            unw.insert(unw.end(), u.begin(), u.end());
-        }
-        for (auto& c : work)   // an SNV candidate the host handed in: its locus is dirty; the other bases of the locus are made below, from the counts
-            if (c.category == PISCES_CAT_SNV && split_dirty_at(h, c.position) && c.alt.size() == 1 && std::binary_search(keys.begin(), keys.end(), block_key(h, c.position)))
-                unw.push_back({c.position, (uint8_t)c.alt[0], {0, 0, 0}});
-        if (max_cleared >= 0) {   // (SNV candidates of held blocks that joined the batch — forced ones: what the reads so far show at their positions)
-            std::vector<int32_t> seen;
-            for (auto& c : work) {
-                if (c.category != PISCES_CAT_SNV || c.position <= max_cleared || std::find(seen.begin(), seen.end(), c.position) != seen.end()) continue;
-                seen.push_back(c.position);
-                auto it = h->blocks.find(block_key(h, c.position));
-                if (it == h->blocks.end()) continue;
-                for (auto& u : it->second.unwalked)
-                    if (u.position == c.position) unw.push_back(u);
-            }
-        }
-        std::sort(unw.begin(), unw.end(), [](const BlockObs::Unwalked& a, const BlockObs::Unwalked& b) { return a.position != b.position ? a.position < b.position : a.alt < b.alt; });
-        size_t w = 0;
-        for (size_t i = 0; i < unw.size(); i++) {
-            if (w > 0 && unw[w - 1].position == unw[i].position && unw[w - 1].alt == unw[i].alt) { for (int d = 0; d < 3; d++) unw[w - 1].sup[d] += unw[i].sup[d]; continue; }
-            unw[w++] = unw[i];
-        }
-        unw.resize(w);
+    std::sort(unw.begin(), unw.end(), [](const BlockObs::Unwalked& a, const BlockObs::Unwalked& b) { return a.position != b.position ? a.position < b.position : a.alt < b.alt; });
+    size_t w = 0;
+    for (size_t i = 0; i < unw.size(); i++) {
+        if (w > 0 && unw[w - 1].position == unw[i].position && unw[w - 1].alt == unw[i].alt) { for (int d = 0; d < 3; d++) unw[w - 1].sup[d] += unw[i].sup[d]; continue; }
+        unw[w++] = unw[i];
     }
-    auto unwalked_of = [&](int32_t position, char alt, int d) -> int32_t {
-        auto it = std::lower_bound(unw.begin(), unw.end(), std::make_pair(position, (uint8_t)alt), [](const BlockObs::Unwalked& u, const std::pair<int32_t, uint8_t>& k) {
-            return u.position != k.first ? u.position < k.first : u.alt < k.second; });
-        return (it != unw.end() && it->position == position && it->alt == (uint8_t)alt) ? it->sup[d] : 0;
-    };
-    if (work.empty() && unw.empty()) return PISCES_OK;
-    // start / end points (CoverageCalculator.Compute :27-41)
-    auto endpoints = [](const HostCandidate& c, int32_t& sp, int32_t& ep) {
-        if (c.category == PISCES_CAT_DELETION) { sp = c.position + 1; ep = c.position + (int32_t)c.ref.size() - 1; }
-        else if (c.category == PISCES_CAT_MNV) { sp = c.position; ep = c.position + (int32_t)c.alt.size() - 1; }
-        else if (c.category == PISCES_CAT_INSERTION) { sp = c.position; ep = c.position + 1; }
-        else { sp = c.position; ep = c.position; }
-    };
-    // ---- where the candidates' counts come from (kernels.hip.h CountsView).  Point alleles, MNVs and deletions add up all anchor bins of a
-    // cell: when the flush's tile kernel has run over these blocks already it left exactly those sums for every locus (h->fold), and no
-    // second walk over the reads is needed for them.  What is left — insertions (their coverage looks at the bins), loci outside that
-    // launch (an allele that ends in a held block), or everything when the tile kernels come later — is accumulated into the tensor, for
-    // the 64-locus tiles those loci lie in only (the read store; with an observation log: the whole blocks, bucketed as they always were).
-    const bool have_forced = !h->forced.empty();
-    const bool fold_ok = blocks_first && h->fold.valid;
-    auto in_fold = [&](int32_t p) { return fold_ok && p >= h->fold.lo && p <= h->fold.hi; };
-    const bool sparse_tiles = h->read_path == 1 && h->log_ub == 0;
-    const int tiles_per_block = (bs + kTile - 1) / kTile;
-    auto tile_start_of = [&](int32_t p) { const int32_t b0 = (block_key(h, p) - 1) * bs + 1; return b0 + ((p - b0) / kTile) * kTile; };
+    unw.resize(w);
+}
+
+// ---- where the candidates' counts come from (kernels.hip.h CountsView).  Point alleles, MNVs and deletions add up all anchor bins of a
+// cell: when the flush's tile kernel has run over these blocks already it left exactly those sums for every locus (h->fold), and no
+// second walk over the reads is needed for them.  What is left — insertions (their coverage looks at the bins), loci outside that
+// launch (an allele that ends in a held block), or everything when the tile kernels come later — is accumulated into the tensor, for
+// the 64-locus tiles those loci lie in only (the read store; with an observation log: the whole blocks, bucketed as they always were).
+static std::vector<int32_t> span_tensor_positions(SpanBatch& B)
+{
+    PiscesHip* h = B.h;
+    B.fold_ok = B.blocks_first && h->fold.valid;
+    B.sparse_tiles = h->read_path == 1 && h->log_ub == 0;
     std::vector<int32_t> need_pos;   // positions whose counts must be in the tensor
     auto need = [&](int32_t p, bool may_fold) {
-        if (p > 0 && !(may_fold && in_fold(p)) && h->blocks.count(block_key(h, p))) need_pos.push_back(p);
+        if (p > 0 && !(may_fold && in_fold(B, p)) && h->blocks.count(block_key(h, p))) need_pos.push_back(p);
     };
-    for (auto& c : work) {
+    for (auto& c : B.work) {
         int32_t sp, ep;
-        endpoints(c, sp, ep);
+        span_endpoints(c, sp, ep);
         const bool may_fold = c.category != PISCES_CAT_INSERTION;
         if (c.category == PISCES_CAT_MNV) { for (int32_t p = sp; p <= ep; p++) need(p, true); }   // (and what reallocation makes of it: SNVs, Reference alleles)
         else { need(sp, may_fold); need(ep, may_fold); }
     }
-    if (have_forced)
+    if (!h->forced.empty())
         for (int32_t p : h->forced_positions)
-            if (std::binary_search(keys.begin(), keys.end(), block_key(h, p))) need(p, true);
-    for (auto& u : unw) need(u.position, true);
-    phase(2);
-    std::vector<PiscesTile> tiles;
-    std::vector<int32_t> bkeys, tile_starts;
-    if (sparse_tiles) {
-        for (int32_t p : need_pos) tile_starts.push_back(tile_start_of(p));
-        std::sort(tile_starts.begin(), tile_starts.end());
-        tile_starts.erase(std::unique(tile_starts.begin(), tile_starts.end()), tile_starts.end());
-        for (int32_t ts : tile_starts) {
+            if (in_batch(B, p)) need(p, true);
+    for (auto& u : B.unw) need(u.position, true);
+    return need_pos;
+}
+
+static int32_t span_count_tiles(SpanBatch& B, const std::vector<int32_t>& need_pos)
+{
+    PiscesHip* h = B.h;
+    const int bs = h->cfg.block_size;
+    const bool window = h->cfg.noise_model == PISCES_NOISE_WINDOW;
+    if (B.sparse_tiles) {
+        for (int32_t p : need_pos) B.tile_starts.push_back(tile_start_of(B, p));
+        std::sort(B.tile_starts.begin(), B.tile_starts.end());
+        B.tile_starts.erase(std::unique(B.tile_starts.begin(), B.tile_starts.end()), B.tile_starts.end());
+        for (int32_t ts : B.tile_starts) {
             PiscesTile t;
             t.start_position = ts;
             t.n_loci = std::min<int32_t>(kTile, block_key(h, ts) * bs - ts + 1);
             t.tuple_begin = t.tuple_end = 0;
-            tiles.push_back(t);
+            B.tiles.push_back(t);
         }
-        if (!tiles.empty()) {
-            PISCES_HIP_CHECK(h, h->d_span_tiles.reserve(tiles.size()));
-            { int32_t rcu = meta_upload(h, h->d_span_tiles.p, tiles.data(), tiles.size() * sizeof(PiscesTile)); if (rcu) return rcu; }
+        if (!B.tiles.empty()) {
+            PISCES_HIP_CHECK(h, h->d_span_tiles.reserve(B.tiles.size()));
+            { int32_t rcu = meta_upload(h, h->d_span_tiles.p, B.tiles.data(), B.tiles.size() * sizeof(PiscesTile)); if (rcu) return rcu; }
         }
     } else {
-        for (int32_t p : need_pos) bkeys.push_back(block_key(h, p));
-        std::sort(bkeys.begin(), bkeys.end());
-        bkeys.erase(std::unique(bkeys.begin(), bkeys.end()), bkeys.end());
+        for (int32_t p : need_pos) B.bkeys.push_back(block_key(h, p));
+        std::sort(B.bkeys.begin(), B.bkeys.end());
+        B.bkeys.erase(std::unique(B.bkeys.begin(), B.bkeys.end()), B.bkeys.end());
         // counts over the whole block grid of those blocks (not the interval-clipped tiles)
-        if (!bkeys.empty()) {
-            int32_t rcb = bucket_blocks(h, bkeys, false, tiles);
+        if (!B.bkeys.empty()) {
+            int32_t rcb = bucket_blocks(h, B.bkeys, false, B.tiles);
             if (rcb) return rcb;
         }
     }
-    const int32_t n_tiles = (int32_t)tiles.size();
-    const PiscesTile* const d_span_tiles = sparse_tiles ? h->d_span_tiles.p : h->d_tiles.p;
-    bool counts_missing = false;
-    auto locus_index = [&](int32_t p, bool may_fold = true) -> int64_t {
-        if (p <= 0) return -1;
-        if (may_fold && in_fold(p)) return -((int64_t)(p - h->fold.lo) + 2);   // the folded counts of the tile kernels' launch
-        const int32_t k = block_key(h, p);
-        if (!h->blocks.count(k)) return -1;   // no block: no counts (RegionStateManager.cs:222-226)
-        if (sparse_tiles) {
-            const int32_t ts = tile_start_of(p);
-            auto it = std::lower_bound(tile_starts.begin(), tile_starts.end(), ts);
-            if (it == tile_starts.end() || *it != ts) { counts_missing = true; return -1; }
-            return (int64_t)(it - tile_starts.begin()) * kTile + (p - ts);
-        }
-        auto it = std::lower_bound(bkeys.begin(), bkeys.end(), k);
-        if (it == bkeys.end() || *it != k) { counts_missing = true; return -1; }
-        const int64_t bi = it - bkeys.begin();
-        const int32_t off = p - ((k - 1) * bs + 1);
-        return (bi * tiles_per_block + off / kTile) * kTile + off % kTile;
-    };
+    const int32_t n_tiles = (int32_t)B.tiles.size();
+    const PiscesTile* const d_span_tiles = B.sparse_tiles ? h->d_span_tiles.p : h->d_tiles.p;
     if (n_tiles > 0) {
         PISCES_HIP_CHECK(h, accumulate_tiles(h, h->stream, h->d_tuples.p, d_span_tiles, n_tiles, window, true));
     } else {
         PISCES_HIP_CHECK(h, h->d_counts.reserve(PISCES_COUNTS_PER_LOCUS));
         if (window) PISCES_HIP_CHECK(h, h->d_sumq.reserve(PISCES_COUNTS_PER_LOCUS));
     }
-    const int32_t* const d_folded = fold_ok ? h->d_folded.p : (const int32_t*)nullptr;
-    auto atype = [](char ch) { return ch == 'A' ? 0 : ch == 'G' ? 1 : ch == 'C' ? 2 : ch == 'T' ? 3 : 4; };
-    auto gapped_at = [&](int32_t p) {
-        auto it = h->gapped_mnv_ref.find(p);
-        return it == h->gapped_mnv_ref.end() ? 0 : it->second;
-    };
-    auto to_dev = [&](const HostCandidate& c, DevCandidate& d) {
-        std::memset(&d, 0, sizeof(d));
-        d.position = c.position;
-        d.category = c.category;
-        d.ref_len = (int32_t)c.ref.size();
-        d.alt_len = (int32_t)c.alt.size();
-        for (int k = 0; k < 3; k++) { d.sup[k] = c.support_by_dir[k]; d.anch[k] = c.well_anchored_by_dir[k]; }
-        d.first_base = d.last_base = PISCES_ALLELE_N;
-        if (c.category == PISCES_CAT_INSERTION && c.alt.size() >= 2) {
-            d.first_base = atype(c.alt[1]);
-            d.last_base = atype(c.alt[c.alt.size() - 1]);
-        }
-        int32_t sp, ep;
-        endpoints(c, sp, ep);
-        const bool may_fold = c.category != PISCES_CAT_INSERTION;
-        d.start_idx = locus_index(sp, may_fold);
-        d.end_idx = locus_index(ep, may_fold);
-        d.gapped = (c.category == PISCES_CAT_SNV || c.category == PISCES_CAT_REFERENCE) ? gapped_at(c.position) : 0;
-    };
-    // The collapser's frequencies and the reallocator's Reference candidates read anchor-resolved counts on the host: the ROWS of the few
-    // loci they can look at (gather_count_rows_kernel), never the tensor — every start / end point when some candidate is open-ended (the
-    // collapser's candidates: CandidateAllele.Frequency of the open-ended one and of what it may join), the positions an MNV candidate
-    // spans (a failed one's Reference candidates, MnvReallocator.cs:12-98), a forced SNV's position.
-    const int32_t* host_counts_p = nullptr;
+    B.d_folded = B.fold_ok ? h->d_folded.p : (const int32_t*)nullptr;
+    return PISCES_OK;
+}
+
+// The collapser's frequencies and the reallocator's Reference candidates read anchor-resolved counts on the host: the ROWS of the few
+// loci they can look at (gather_count_rows_kernel), never the tensor — every start / end point when some candidate is open-ended (the
+// collapser's candidates: CandidateAllele.Frequency of the open-ended one and of what it may join), the positions an MNV candidate
+// spans (a failed one's Reference candidates, MnvReallocator.cs:12-98), a forced SNV's position.
+static int32_t span_count_rows(SpanBatch& B)
+{
+    PiscesHip* h = B.h;
     std::unordered_map<int64_t, int32_t>& row_of = h->row_of_locus;
     row_of.clear();
-    bool rows_missing = false;
-    auto row_index = [&](int64_t li) -> int64_t {
-        if (li == -1) return -1;
-        auto it = row_of.find(li);
-        if (it == row_of.end()) { rows_missing = true; return -1; }
-        return it->second;
-    };
-    {
-        bool any_open = false;
-        if (h->cfg.collapse)
-            for (auto& c : work) any_open = any_open || c.open_left || c.open_right;
-        std::vector<long long> need;
-        auto want = [&](int32_t p, bool may_fold) { const int64_t li = locus_index(p, may_fold); if (li != -1) need.push_back(li); };
-        for (auto& c : work) {
-            int32_t sp, ep;
-            endpoints(c, sp, ep);
-            const bool may_fold = c.category != PISCES_CAT_INSERTION;
-            if (mnv_mode && c.category == PISCES_CAT_MNV)
-                for (int32_t p = sp; p <= ep; p++) want(p, true);
-            else if (any_open || ((have_forced || !h->snv_walk) && c.category == PISCES_CAT_SNV)) { want(sp, may_fold); want(ep, may_fold); }
-        }
-        for (auto& u : unw) want(u.position, true);
-        std::sort(need.begin(), need.end());
-        need.erase(std::unique(need.begin(), need.end()), need.end());
-        const size_t n_rows = need.size(), n_counts = std::max<size_t>(n_rows, 1) * PISCES_COUNTS_PER_LOCUS;
-        if (n_counts > h->h_counts_cap) {
-            if (h->h_counts) host_free(h->h_counts);
-            h->h_counts = nullptr;
-            h->h_counts_cap = 0;
-            PISCES_HIP_CHECK(h, host_alloc((void**)&h->h_counts, (n_counts + n_counts / 2) * sizeof(int32_t)));
-            h->h_counts_cap = n_counts + n_counts / 2;
-        }
-        if (n_rows > 0) {
-            for (size_t k = 0; k < n_rows; k++) row_of.emplace(need[k], (int32_t)k);
-            PISCES_HIP_CHECK(h, h->d_row_idx.reserve(n_rows));
-            PISCES_HIP_CHECK(h, h->d_rows.reserve(n_rows * PISCES_COUNTS_PER_LOCUS));
-            { int32_t rcu = meta_upload(h, h->d_row_idx.p, need.data(), n_rows * sizeof(long long)); if (rcu) return rcu; }
-            hipLaunchKernelGGL(gather_count_rows_kernel, dim3((unsigned)((n_rows * PISCES_COUNTS_PER_LOCUS + 255) / 256)), dim3(256), 0, h->stream,
-                               (const int32_t*)h->d_counts.p, d_folded, (const long long*)h->d_row_idx.p, (int32_t)n_rows, h->d_rows.p);
-            PISCES_HIP_CHECK(h, hipGetLastError());
-            h->pcie[3] += (int64_t)(n_rows * PISCES_COUNTS_PER_LOCUS * sizeof(int32_t));
-            PISCES_HIP_CHECK(h, hipMemcpyAsync(h->h_counts, h->d_rows.p, n_rows * PISCES_COUNTS_PER_LOCUS * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-            PISCES_TIMED_WAIT(h, hipStreamSynchronize(h->stream));
-        }
-        host_counts_p = h->h_counts;
+    bool any_open = false;
+    if (h->cfg.collapse)
+        for (auto& c : B.work) any_open = any_open || c.open_left || c.open_right;
+    const bool have_forced = !h->forced.empty();
+    std::vector<long long> need;
+    auto want = [&](int32_t p, bool may_fold) { const int64_t li = locus_index(B, p, may_fold); if (li != -1) need.push_back(li); };
+    for (auto& c : B.work) {
+        int32_t sp, ep;
+        span_endpoints(c, sp, ep);
+        const bool may_fold = c.category != PISCES_CAT_INSERTION;
+        if (h->cfg.call_mnvs != 0 && c.category == PISCES_CAT_MNV)
+            for (int32_t p = sp; p <= ep; p++) want(p, true);
+        else if (any_open || ((have_forced || !h->snv_walk) && c.category == PISCES_CAT_SNV)) { want(sp, may_fold); want(ep, may_fold); }
     }
-    struct { const int32_t* p; const int32_t* data() const { return p; } } host_counts = {host_counts_p};
-    if (!h->snv_walk) {
-        // MNV calling off: the reads' SNV candidates are the allele counts and never reach the host, so an SNV candidate that IS an object
-        // here — a forced allele (added without support), one the host handed in (with its own) — takes the support the merged candidate of
-        // the reference has: the reads that show the base at or above the quality threshold join it
-        for (auto& c : work) {
-            if (c.category != PISCES_CAT_SNV || c.alt.size() != 1 || c.counted_by_dir[0] + c.counted_by_dir[1] + c.counted_by_dir[2] != 0) continue;
-            const int64_t li = row_index(locus_index(c.position));
-            const int at = atype(c.alt[0]);
-            if (li < 0 || at >= 4) continue;
-            for (int d = 0; d < 3; d++) {
-                const int32_t* row = host_counts.data() + li * PISCES_COUNTS_PER_LOCUS + (at * 3 + d) * PISCES_NUM_ANCHORS;
-                const int32_t own = c.support_by_dir[d];
-                for (int an = 0; an < PISCES_NUM_ANCHORS; an++) c.support_by_dir[d] += row[an];
-                c.support_by_dir[d] = std::max(own, c.support_by_dir[d] - unwalked_of(c.position, c.alt[0], d));   // (less what no candidate stands for)
-                c.counted_by_dir[d] = c.support_by_dir[d] - own;
-            }
-        }
+    for (auto& u : B.unw) want(u.position, true);
+    std::sort(need.begin(), need.end());
+    need.erase(std::unique(need.begin(), need.end()), need.end());
+    const size_t n_rows = need.size(), n_counts = std::max<size_t>(n_rows, 1) * PISCES_COUNTS_PER_LOCUS;
+    if (n_counts > h->h_counts_cap) {
+        if (h->h_counts) host_free(h->h_counts);
+        h->h_counts = nullptr;
+        h->h_counts_cap = 0;
+        PISCES_HIP_CHECK(h, host_alloc((void**)&h->h_counts, (n_counts + n_counts / 2) * sizeof(int32_t)));
+        h->h_counts_cap = n_counts + n_counts / 2;
     }
-    phase(3);
-    if (h->cfg.collapse) {
-        const int32_t stitched = h->cfg.expect_stitched_reads;
-        *n_collapsed = collapse_candidates(work, h->cfg.collapse_freq_threshold, h->cfg.collapse_freq_ratio_threshold, [&](const HostCandidate& c) {
-            DevCandidate d;
-            to_dev(c, d);
-            d.start_idx = row_index(d.start_idx);   // (rows of the gathered loci, not of the tensor)
-            d.end_idx = row_index(d.end_idx);
-            const int total = candidate_total_coverage(d, host_counts.data(), stitched);
-            const int support = c.support_by_dir[0] + c.support_by_dir[1] + c.support_by_dir[2];
-            if (total == 0) return 0.0f;                       // CalledAllele.Frequency (CalledAllele.cs:49-52)
-            const float f = (float)support / (float)total;
-            return f < 1.0f ? f : 1.0f;
-        }, &h->known_variants, h->exclude_mnvs_from_collapsing);
-        // candidates past the last cleared position that could not be collapsed return to the state (VariantCollapser.cs:67-75): only the
-        // ones AddCollapsableFromOtherBlocks brought in can lie there
-        if (max_cleared >= 0) {
-            size_t w = 0;
-            for (size_t i = 0; i < work.size(); i++) {
-                if (work[i].position > max_cleared && work[i].category != PISCES_CAT_REFERENCE) {
-                    for (int d = 0; d < 3; d++) { work[i].support_by_dir[d] -= work[i].counted_by_dir[d]; work[i].counted_by_dir[d] = 0; }   // (the allele counts are asked again when its block is flushed)
-                    work[i].stamp = next_host_stamp(h);   // (AddCandidates appends it to its position's list again)
-                    add_candidate(h, work[i]);
-                    continue;
-                }
-                if (w != i) work[w] = std::move(work[i]);
-                w++;
-            }
-            work.resize(w);
-            if (work.empty() && unw.empty()) return PISCES_OK;
-        }
-    }
-    if (!unw.empty()) {
-        // the SNV candidates of the loci with unwalked bases: what the reads show there (the counts) less those bases
-        static const char kAcgt[4] = {'A', 'C', 'G', 'T'};
-        const size_t n_before = work.size();
-        std::unordered_set<uint64_t> snv_there;   // (position, base) of the SNV candidates that are objects already: forced alleles, the host's (support taken above)
-        for (auto& c : work)
-            if (c.category == PISCES_CAT_SNV && c.alt.size() == 1) snv_there.insert(((uint64_t)(uint32_t)c.position << 8) | (uint8_t)c.alt[0]);
-        for (size_t i = 0; i < unw.size();) {
-            const int32_t p = unw[i].position;
-            while (i < unw.size() && unw[i].position == p) i++;
-            if (p < 1 || (int64_t)p > h->ref_len || !std::binary_search(keys.begin(), keys.end(), block_key(h, p))) continue;
-            const char rb = (char)h->h_ref[(size_t)p - 1];
-            const int64_t li = row_index(locus_index(p));
-            if (atype(rb) >= 4 || li < 0) continue;
-            for (char ab : kAcgt) {
-                if (ab == rb) continue;
-                if (snv_there.count(((uint64_t)(uint32_t)p << 8) | (uint8_t)ab)) continue;
-                HostCandidate c;
-                c.position = p;
-                c.category = PISCES_CAT_SNV;
-                c.ref.assign(1, rb);
-                c.alt.assign(1, ab);
-                int32_t total = 0;
-                for (int d = 0; d < 3; d++) {
-                    const int32_t* row = host_counts.data() + li * PISCES_COUNTS_PER_LOCUS + (atype(ab) * 3 + d) * PISCES_NUM_ANCHORS;
-                    int32_t n = 0;
-                    for (int an = 0; an < PISCES_NUM_ANCHORS; an++) n += row[an];
-                    n = std::max(0, n - unwalked_of(p, ab, d));
-                    c.support_by_dir[d] = c.well_anchored_by_dir[d] = n;
-                    total += n;
-                }
-                if (total <= 0) continue;   // no read walk made a candidate of this allele
-                c.stamp = next_host_stamp(h);
-                c.from_reads = true;
-                work.push_back(std::move(c));
-            }
-        }
-        if (work.size() != n_before)
-            std::stable_sort(work.begin(), work.end(), [](const HostCandidate& x, const HostCandidate& y) { return x.position < y.position; });
-        if (work.empty()) return PISCES_OK;
-    }
-    // one device pass over a list of candidates: records + IsCallable
-    std::vector<PiscesCalledAllele> raw;
-    std::vector<uint8_t> callable;
-    bool second_pass = false;   // MNV mode: the pass over every callable allele, after the MNV-only pass
-    // wanted: what the caller reads of the pass (call_spanning_kernel's kSpanning*): the records of alleles that are not callable only
-    // matter for forced alleles, and the MNV pass reads IsCallable alone
-    auto device_pass = [&](const std::vector<const HostCandidate*>& list, int32_t wanted) -> int32_t {
-        std::vector<DevCandidate> dc(list.size());
-        std::vector<uint8_t> pool;
-        for (size_t i = 0; i < list.size(); i++) {
-            to_dev(*list[i], dc[i]);
-            dc[i].reprocessed = (second_pass && list[i]->category == PISCES_CAT_MNV && !work.empty() && list[i] >= work.data() &&
-                                 list[i] < work.data() + work.size()) ? 1 : 0;
-            dc[i].allele_off = (int32_t)pool.size();
-            pool.insert(pool.end(), list[i]->ref.begin(), list[i]->ref.end());
-            pool.insert(pool.end(), list[i]->alt.begin(), list[i]->alt.end());
-        }
-        raw.assign(dc.size(), PiscesCalledAllele{});
-        callable.assign(dc.size(), 0);
-        if (dc.empty()) return PISCES_OK;
-        const int32_t n = (int32_t)dc.size();
-        PISCES_HIP_CHECK(h, h->d_cands.reserve(dc.size()));
-        PISCES_HIP_CHECK(h, h->d_alleles.reserve(pool.size() + 16));
-        PISCES_HIP_CHECK(h, h->d_cand_records.reserve(dc.size()));
-        PISCES_HIP_CHECK(h, h->d_cand_callable.reserve(dc.size()));
-        // (through the pinned arena and into a pinned buffer: a transfer from or to pageable memory is staged by the runtime, and the host
-        // waits for it)
-        { int32_t rcu = meta_upload(h, h->d_cands.p, dc.data(), dc.size() * sizeof(DevCandidate)); if (rcu) return rcu; }
-        { int32_t rcu = meta_upload(h, h->d_alleles.p, pool.data(), pool.size()); if (rcu) return rcu; }
-        hipLaunchKernelGGL(call_spanning_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, h->stream, h->d_cands.p, n, h->d_counts.p,
-                           h->d_alleles.p, h->d_ref.p, h->ref_len, h->cfg.expect_stitched_reads, h->d_cand_records.p, h->d_cand_callable.p, h->P,
-                           window ? h->d_sumq.p : (const double*)nullptr, d_folded, wanted);
+    if (n_rows > 0) {
+        for (size_t k = 0; k < n_rows; k++) row_of.emplace(need[k], (int32_t)k);
+        PISCES_HIP_CHECK(h, h->d_row_idx.reserve(n_rows));
+        PISCES_HIP_CHECK(h, h->d_rows.reserve(n_rows * PISCES_COUNTS_PER_LOCUS));
+        { int32_t rcu = meta_upload(h, h->d_row_idx.p, need.data(), n_rows * sizeof(long long)); if (rcu) return rcu; }
+        hipLaunchKernelGGL(gather_count_rows_kernel, dim3((unsigned)((n_rows * PISCES_COUNTS_PER_LOCUS + 255) / 256)), dim3(256), 0, h->stream,
+                           (const int32_t*)h->d_counts.p, B.d_folded, (const long long*)h->d_row_idx.p, (int32_t)n_rows, h->d_rows.p);
         PISCES_HIP_CHECK(h, hipGetLastError());
-        const size_t rec_bytes = wanted == kSpanningFlagsOnly ? 0 : raw.size() * sizeof(PiscesCalledAllele), need = rec_bytes + callable.size();
-        h->pcie[1] += (int64_t)need;
-        if (need > h->h_cand_dl_cap) {
-            if (h->h_cand_dl) host_free(h->h_cand_dl);
-            h->h_cand_dl = nullptr;
-            h->h_cand_dl_cap = 0;
-            PISCES_HIP_CHECK(h, host_alloc((void**)&h->h_cand_dl, need + need / 2));
-            h->h_cand_dl_cap = need + need / 2;
-        }
-        if (rec_bytes) PISCES_HIP_CHECK(h, hipMemcpyAsync(h->h_cand_dl, h->d_cand_records.p, rec_bytes, hipMemcpyDeviceToHost, h->stream));
-        PISCES_HIP_CHECK(h, hipMemcpyAsync(h->h_cand_dl + rec_bytes, h->d_cand_callable.p, callable.size(), hipMemcpyDeviceToHost, h->stream));
+        h->pcie[3] += (int64_t)(n_rows * PISCES_COUNTS_PER_LOCUS * sizeof(int32_t));
+        PISCES_HIP_CHECK(h, hipMemcpyAsync(h->h_counts, h->d_rows.p, n_rows * PISCES_COUNTS_PER_LOCUS * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
         PISCES_TIMED_WAIT(h, hipStreamSynchronize(h->stream));
-        std::memcpy(raw.data(), h->h_cand_dl, rec_bytes);
-        std::memcpy(callable.data(), h->h_cand_dl + rec_bytes, callable.size());
-        return PISCES_OK;
-    };
-    auto owned = [&](int32_t position) { return position >= h->own_lo && position <= h->own_hi; };   // (interval sharding: pisces_hip_set_owned_range)
-    auto inside_intervals = [&](int32_t position) {   // ShouldReport (AlleleCaller.cs:260-263)
-        if (!owned(position)) return false;
-        if (h->intervals.empty()) return true;
-        auto it = std::lower_bound(h->intervals.begin(), h->intervals.end(), position,
-                                   [](const std::pair<int32_t, int32_t>& iv, int32_t p) { return iv.second < p; });
-        return it != h->intervals.end() && it->first <= position;
-    };
-
-    phase(4);
-    std::vector<const HostCandidate*> final_list;
-    MnvArena arena;
-    std::vector<CandPtr> callable_alleles;          // AlleleCaller's callableAlleles (non-Reference ones and touched Reference ones)
-    std::map<int32_t, CandPtr> touched_refs;         // Reference candidates created for the reallocator, by position
-    if (!mnv_mode) {
-        for (auto& c : work) final_list.push_back(&c);
-    } else {
-        // ---- MNV candidates first (AlleleCaller.cs:69-89)
-        std::vector<const HostCandidate*> mnvs;
-        for (auto& c : work)
-            if (c.category == PISCES_CAT_MNV) mnvs.push_back(&c);
-        int32_t rc1 = device_pass(mnvs, kSpanningFlagsOnly);
-        if (rc1) return rc1;
-        phase(5);
-        std::vector<CandPtr> failed;
-        {
-            size_t mi = 0;
-            for (auto& c : work) {
-                if (c.category == PISCES_CAT_MNV) {
-                    if (callable[mi]) { callable_alleles.push_back(&c); if (owned(c.position)) (*n_called)++; }   // IsCallable counts every pass (_totalNumCalled)
-                    else failed.push_back(&c);
-                    mi++;
-                } else {
-                    callable_alleles.push_back(&c);
-                }
-            }
-        }
-        if (!failed.empty()) {
-            // Reference candidates of this batch that a failed MNV can reach: only those whose base equals the MNV's base there can
-            // match (OverlapMatches); their AlleleSupport (the reference base's counts) decides the order among one-base overlaps
-            const int32_t last_cleared = keys.back() * bs;
-            auto ref_candidate_exists = [&](int32_t p, int32_t (&sup)[3]) {
-                // (not a gVCF: Reference candidates exist at the positions of the forced alleles only, RegionState.cs:393-396)
-                const bool forced_here = !h->cfg.include_reference_calls && h->forced_positions.count(p) != 0;
-                if (!(h->cfg.include_reference_calls || forced_here) || p < 1 || p > h->ref_len || !inside_intervals(p)) return false;
-                if (!std::binary_search(keys.begin(), keys.end(), block_key(h, p))) return false;
-                const int64_t li = row_index(locus_index(p));
-                const int rb = atype((char)h->h_ref[(size_t)p - 1]);
-                int total = 0;
-                sup[0] = sup[1] = sup[2] = 0;
-                if (li >= 0)
-                    for (int at = 0; at < PISCES_NUM_ALLELE_TYPES; at++)
-                        for (int d = 0; d < 3; d++) {
-                            int cnt = 0;
-                            const int32_t* row = host_counts.data() + li * PISCES_COUNTS_PER_LOCUS + (at * 3 + d) * PISCES_NUM_ANCHORS;
-                            for (int an = 0; an < PISCES_NUM_ANCHORS; an++) cnt += row[an];
-                            if (at == rb) sup[d] = cnt;
-                            total += cnt;
-                        }
-                return h->cfg.emit_zero_coverage_refs != 0 || forced_here || total > 0;   // RegionState.cs:446
-            };
-            for (CandPtr f : failed)
-                for (size_t k = 0; k < f->alt.size(); k++) {
-                    const int32_t p = f->position + (int32_t)k;
-                    if (f->alt[k] != f->ref[k] || touched_refs.count(p)) continue;
-                    int32_t sup[3];
-                    if (!ref_candidate_exists(p, sup)) continue;
-                    CandPtr rc = arena.make(p, std::string(1, f->ref[k]), std::string(1, f->ref[k]), sup);
-                    touched_refs[p] = rc;
-                }
-            // GetAllCandidates appends the Reference candidates after the variant candidates of a block: the order only matters for
-            // ties between alleles of equal length, support and bases, which Reference candidates (base == reference) cannot have with
-            // a variant; among themselves they are in position order
-            std::vector<CandPtr> ref_originals;
-            std::vector<std::array<int32_t, 3>> ref_before;
-            for (auto& kv : touched_refs) {
-                callable_alleles.push_back(kv.second);
-                ref_originals.push_back(kv.second);
-                ref_before.push_back({kv.second->support_by_dir[0], kv.second->support_by_dir[1], kv.second->support_by_dir[2]});
-            }
-            std::vector<CandPtr> outside;
-            { HostTimer prof_r(h->prof_on ? &h->prof[11] : nullptr); mnv_reallocate_failed(arena, failed, callable_alleles, true, last_cleared, outside); }
-            for (CandPtr o : outside)   // source.AddCandidates(leftovers.Select(AlleleHelper.Map)) :92-93
-                if (o->category != PISCES_CAT_REFERENCE && o->position > 0) {
-                    HostCandidate c = *o;
-                    c.well_anchored_by_dir[0] = c.well_anchored_by_dir[1] = c.well_anchored_by_dir[2] = 0;
-                    c.open_left = c.open_right = false;
-                    c.stamp = next_host_stamp(h);
-                    c.from_reads = false;   // (support that reallocation moved: no longer what the allele counts say)
-                    add_candidate(h, c);
-                }
-            // Reference candidates keep only what reallocation added: the kernel supplies their own counts
-            for (size_t i = 0; i < ref_originals.size(); i++)
-                for (int d = 0; d < 3; d++) ref_originals[i]->support_by_dir[d] -= ref_before[i][(size_t)d];
-        }
-        // GetRefSupportFromGappedMnvs :180-203 -> IAlleleSource.AddGappedMnvRefCount
-        std::vector<int32_t> gapped_now;
-        for (CandPtr a : callable_alleles) {
-            if (a->category != PISCES_CAT_MNV) continue;
-            const int support = cand_support(*a);
-            for (size_t k = 0; k < a->ref.size() && k < a->alt.size(); k++)
-                if (a->ref[k] == a->alt[k]) { h->gapped_mnv_ref[a->position + (int32_t)k] += support; gapped_now.push_back(a->position + (int32_t)k); }
-        }
-        // The tile kernels of this flush ran before these counts existed: the Reference allele of such a position (its support less what the
-        // gapped MNVs take, CoverageCalculator.cs:82-97) comes from the candidate kernel and replaces theirs.  (SNVs of the position are
-        // candidates of this pass anyway: an MNV spans it.)
-        std::vector<CandPtr> gapped_refs;
-        if (blocks_first) {
-            std::sort(gapped_now.begin(), gapped_now.end());
-            gapped_now.erase(std::unique(gapped_now.begin(), gapped_now.end()), gapped_now.end());
-            static const int32_t kNoSupport[3] = {0, 0, 0};
-            for (int32_t p : gapped_now) {
-                if (touched_refs.count(p)) { if (cand_support(*touched_refs[p]) == 0) gapped_refs.push_back(touched_refs[p]); continue; }
-                if (!h->cfg.include_reference_calls || p < 1 || p > h->ref_len || !std::binary_search(keys.begin(), keys.end(), block_key(h, p))) continue;
-                touched_refs[p] = arena.make(p, std::string(1, (char)h->h_ref[(size_t)p - 1]), std::string(1, (char)h->h_ref[(size_t)p - 1]), kNoSupport);
-                gapped_refs.push_back(touched_refs[p]);
-            }
-        }
-        // a failed MNV that is a forced allele is reported all the same (AlleleCaller.cs:98-107)
-        if (have_forced)
-            for (CandPtr f : failed)
-                if (is_forced_allele(h, *f)) callable_alleles.push_back(f);
-        for (CandPtr a : callable_alleles) {
-            if (a->category == PISCES_CAT_REFERENCE && cand_support(*a) == 0) continue;   // untouched: the tile kernels' record stands
-            final_list.push_back(a);
-        }
-        for (CandPtr a : gapped_refs) final_list.push_back(a);
     }
-    // not a gVCF, forced alleles given: Reference candidates at the forced positions of the cleared blocks, with or without coverage
-    // (RegionState.GetAllCandidates :393-450 with CreateIntervalsFromAllels); the candidate kernel makes their records from the counts
-    if (have_forced && !h->cfg.include_reference_calls) {
-        static const int32_t kNone[3] = {0, 0, 0};
-        for (int32_t p : h->forced_positions) {
-            if (p < 1 || p > h->ref_len || !inside_intervals(p) || !std::binary_search(keys.begin(), keys.end(), block_key(h, p))) continue;
-            if (touched_refs.count(p)) {
-                if (cand_support(*touched_refs[p]) != 0) continue;   // in the list already, with what reallocation added
-            } else {
-                touched_refs[p] = arena.make(p, std::string(1, (char)h->h_ref[(size_t)p - 1]), std::string(1, (char)h->h_ref[(size_t)p - 1]), kNone);
-            }
-            final_list.push_back(touched_refs[p]);
+    B.host_counts = h->h_counts;
+    if (h->snv_walk) return PISCES_OK;
+    // MNV calling off: the reads' SNV candidates are the allele counts and never reach the host, so an SNV candidate that IS an object
+    // here — a forced allele (added without support), one the host handed in (with its own) — takes the support the merged candidate of
+    // the reference has: the reads that show the base at or above the quality threshold join it
+    for (auto& c : B.work) {
+        if (c.category != PISCES_CAT_SNV || c.alt.size() != 1 || c.counted_by_dir[0] + c.counted_by_dir[1] + c.counted_by_dir[2] != 0) continue;
+        const int64_t li = row_index(B, locus_index(B, c.position));
+        const int at = span_atype(c.alt[0]);
+        if (li < 0 || at >= 4) continue;
+        for (int d = 0; d < 3; d++) {
+            const int32_t own = c.support_by_dir[d];
+            c.support_by_dir[d] += row_count(B, li, at, d);
+            c.support_by_dir[d] = std::max(own, c.support_by_dir[d] - unwalked_of(B, c.position, c.alt[0], d));   // (less what no candidate stands for)
+            c.counted_by_dir[d] = c.support_by_dir[d] - own;
         }
     }
+    return PISCES_OK;
+}
 
-    if (rows_missing || counts_missing) return fail(h, PISCES_E_INTERNAL, "flush: a candidate's counts were not among those made for the batch");
-    phase(6);
-    second_pass = mnv_mode;
-    int32_t rc2 = device_pass(final_list, have_forced ? kSpanningEveryRecord : kSpanningCallableRecords);
-    if (rc2) return rc2;
-    for (size_t i = 0; i < final_list.size(); i++) {
-        if (final_list[i]->category == PISCES_CAT_REFERENCE) {   // counted as called by the tile kernels already (gVCF)
-            ref_overrides.push_back(raw[i]);
+// VariantCollapser; candidates past the last cleared position that could not be collapsed return to the state (VariantCollapser.cs:67-75):
+// only the ones AddCollapsableFromOtherBlocks brought in can lie there
+static void span_collapse(SpanBatch& B, int64_t* n_collapsed)
+{
+    PiscesHip* h = B.h;
+    const int32_t stitched = h->cfg.expect_stitched_reads;
+    *n_collapsed = collapse_candidates(B.work, h->cfg.collapse_freq_threshold, h->cfg.collapse_freq_ratio_threshold, [&](const HostCandidate& c) {
+        DevCandidate d;
+        to_dev(B, c, d);
+        d.start_idx = row_index(B, d.start_idx);   // (rows of the gathered loci, not of the tensor)
+        d.end_idx = row_index(B, d.end_idx);
+        const int total = candidate_total_coverage(d, B.host_counts, stitched);
+        const int support = c.support_by_dir[0] + c.support_by_dir[1] + c.support_by_dir[2];
+        if (total == 0) return 0.0f;                       // CalledAllele.Frequency (CalledAllele.cs:49-52)
+        const float f = (float)support / (float)total;
+        return f < 1.0f ? f : 1.0f;
+    }, &h->known_variants, h->exclude_mnvs_from_collapsing);
+    if (B.max_cleared < 0) return;
+    std::vector<HostCandidate>& work = B.work;
+    size_t w = 0;
+    for (size_t i = 0; i < work.size(); i++) {
+        if (work[i].position > B.max_cleared && work[i].category != PISCES_CAT_REFERENCE) {
+            for (int d = 0; d < 3; d++) { work[i].support_by_dir[d] -= work[i].counted_by_dir[d]; work[i].counted_by_dir[d] = 0; }   // (the allele counts are asked again when its block is flushed)
+            work[i].stamp = next_host_stamp(h);   // (AddCandidates appends it to its position's list again)
+            add_candidate(h, work[i]);
             continue;
         }
-        // AlleleCaller.cs:109-131: a forced allele is reported whether it is callable or not; IsCallable runs once in the test for
-        // IsForcedToReport and once in the test for reporting, and counts a callable forced allele twice in TotalNumCalled
-        const bool forced = have_forced && is_forced_allele(h, *final_list[i]);
-        const bool reportable = callable[i] && inside_intervals(final_list[i]->position);
-        if (callable[i] && owned(final_list[i]->position)) (*n_called) += forced ? 2 : 1;
-        if (forced && !h->snv_walk && final_list[i]->category == PISCES_CAT_SNV && reportable && !split_dirty_at(h, final_list[i]->position)) {   // MNV calling off: the tile kernels report it,
-            (*n_called)--;                                                                        // and have counted it once
+        if (w != i) work[w] = std::move(work[i]);
+        w++;
+    }
+    work.resize(w);
+}
+
+// the SNV candidates of the loci with unwalked bases: what the reads show there (the counts) less those bases
+static void span_unwalked_snvs(SpanBatch& B)
+{
+    PiscesHip* h = B.h;
+    std::vector<HostCandidate>& work = B.work;
+    static const char kAcgt[4] = {'A', 'C', 'G', 'T'};
+    const size_t n_before = work.size();
+    std::unordered_set<uint64_t> snv_there;   // (position, base) of the SNV candidates that are objects already: forced alleles, the host's (support taken before)
+    for (auto& c : work)
+        if (c.category == PISCES_CAT_SNV && c.alt.size() == 1) snv_there.insert(((uint64_t)(uint32_t)c.position << 8) | (uint8_t)c.alt[0]);
+    for (size_t i = 0; i < B.unw.size();) {
+        const int32_t p = B.unw[i].position;
+        while (i < B.unw.size() && B.unw[i].position == p) i++;
+        if (p < 1 || (int64_t)p > h->ref_len || !in_batch(B, p)) continue;
+        const char rb = (char)h->h_ref[(size_t)p - 1];
+        const int64_t li = row_index(B, locus_index(B, p));
+        if (span_atype(rb) >= 4 || li < 0) continue;
+        for (char ab : kAcgt) {
+            if (ab == rb) continue;
+            if (snv_there.count(((uint64_t)(uint32_t)p << 8) | (uint8_t)ab)) continue;
+            HostCandidate c;
+            c.position = p;
+            c.category = PISCES_CAT_SNV;
+            c.ref.assign(1, rb);
+            c.alt.assign(1, ab);
+            int32_t total = 0;
+            for (int d = 0; d < 3; d++) {
+                const int32_t n = std::max(0, row_count(B, li, span_atype(ab), d) - unwalked_of(B, p, ab, d));
+                c.support_by_dir[d] = c.well_anchored_by_dir[d] = n;
+                total += n;
+            }
+            if (total <= 0) continue;   // no read walk made a candidate of this allele
+            c.stamp = next_host_stamp(h);
+            c.from_reads = true;
+            work.push_back(std::move(c));
+        }
+    }
+    if (work.size() != n_before)
+        std::stable_sort(work.begin(), work.end(), [](const HostCandidate& x, const HostCandidate& y) { return x.position < y.position; });
+}
+
+// one device pass over a list of candidates: records + IsCallable into B.raw / B.callable.  wanted: what the caller reads of the pass
+// (call_spanning_kernel's kSpanning*): the records of alleles that are not callable only matter for forced alleles, and the MNV pass reads
+// IsCallable alone
+static int32_t span_device_pass(SpanBatch& B, const std::vector<const HostCandidate*>& list, int32_t wanted)
+{
+    PiscesHip* h = B.h;
+    const bool window = h->cfg.noise_model == PISCES_NOISE_WINDOW;
+    std::vector<DevCandidate> dc(list.size());
+    std::vector<uint8_t> pool;
+    for (size_t i = 0; i < list.size(); i++) {
+        to_dev(B, *list[i], dc[i]);
+        dc[i].reprocessed = (B.second_pass && list[i]->category == PISCES_CAT_MNV && !B.work.empty() && list[i] >= B.work.data() &&
+                             list[i] < B.work.data() + B.work.size()) ? 1 : 0;
+        dc[i].allele_off = (int32_t)pool.size();
+        pool.insert(pool.end(), list[i]->ref.begin(), list[i]->ref.end());
+        pool.insert(pool.end(), list[i]->alt.begin(), list[i]->alt.end());
+    }
+    B.raw.assign(dc.size(), PiscesCalledAllele{});
+    B.callable.assign(dc.size(), 0);
+    if (dc.empty()) return PISCES_OK;
+    const int32_t n = (int32_t)dc.size();
+    PISCES_HIP_CHECK(h, h->d_cands.reserve(dc.size()));
+    PISCES_HIP_CHECK(h, h->d_alleles.reserve(pool.size() + 16));
+    PISCES_HIP_CHECK(h, h->d_cand_records.reserve(dc.size()));
+    PISCES_HIP_CHECK(h, h->d_cand_callable.reserve(dc.size()));
+    // (through the pinned arena and into a pinned buffer: a transfer from or to pageable memory is staged by the runtime, and the host
+    // waits for it)
+    { int32_t rcu = meta_upload(h, h->d_cands.p, dc.data(), dc.size() * sizeof(DevCandidate)); if (rcu) return rcu; }
+    { int32_t rcu = meta_upload(h, h->d_alleles.p, pool.data(), pool.size()); if (rcu) return rcu; }
+    hipLaunchKernelGGL(call_spanning_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, h->stream, h->d_cands.p, n, h->d_counts.p,
+                       h->d_alleles.p, h->d_ref.p, h->ref_len, h->cfg.expect_stitched_reads, h->d_cand_records.p, h->d_cand_callable.p, h->P,
+                       window ? h->d_sumq.p : (const double*)nullptr, B.d_folded, wanted);
+    PISCES_HIP_CHECK(h, hipGetLastError());
+    const size_t rec_bytes = wanted == kSpanningFlagsOnly ? 0 : B.raw.size() * sizeof(PiscesCalledAllele), need = rec_bytes + B.callable.size();
+    h->pcie[1] += (int64_t)need;
+    if (need > h->h_cand_dl_cap) {
+        if (h->h_cand_dl) host_free(h->h_cand_dl);
+        h->h_cand_dl = nullptr;
+        h->h_cand_dl_cap = 0;
+        PISCES_HIP_CHECK(h, host_alloc((void**)&h->h_cand_dl, need + need / 2));
+        h->h_cand_dl_cap = need + need / 2;
+    }
+    if (rec_bytes) PISCES_HIP_CHECK(h, hipMemcpyAsync(h->h_cand_dl, h->d_cand_records.p, rec_bytes, hipMemcpyDeviceToHost, h->stream));
+    PISCES_HIP_CHECK(h, hipMemcpyAsync(h->h_cand_dl + rec_bytes, h->d_cand_callable.p, B.callable.size(), hipMemcpyDeviceToHost, h->stream));
+    PISCES_TIMED_WAIT(h, hipStreamSynchronize(h->stream));
+    std::memcpy(B.raw.data(), h->h_cand_dl, rec_bytes);
+    std::memcpy(B.callable.data(), h->h_cand_dl + rec_bytes, B.callable.size());
+    return PISCES_OK;
+}
+
+// ---- MNV candidates first (AlleleCaller.cs:69-89): the pass that tells the callable ones from the ones that fail
+static int32_t span_mnv_pass(SpanBatch& B)
+{
+    std::vector<const HostCandidate*> mnvs;
+    for (auto& c : B.work)
+        if (c.category == PISCES_CAT_MNV) mnvs.push_back(&c);
+    return span_device_pass(B, mnvs, kSpanningFlagsOnly);
+}
+
+// the callable alleles of the MNV pass, and MnvReallocator for the MNVs that failed (span_reallocate)
+static void span_sort_mnv_pass(SpanBatch& B, int64_t* n_called)
+{
+    size_t mi = 0;
+    for (auto& c : B.work) {
+        if (c.category == PISCES_CAT_MNV) {
+            if (B.callable[mi]) { B.callable_alleles.push_back(&c); if (owned(B.h, c.position)) (*n_called)++; }   // IsCallable counts every pass (_totalNumCalled)
+            else B.failed.push_back(&c);
+            mi++;
+        } else {
+            B.callable_alleles.push_back(&c);
+        }
+    }
+}
+
+// MnvReallocator for the MNVs that failed, with the Reference candidates of this batch that a failed MNV can reach: only those whose base
+// equals the MNV's base there can match (OverlapMatches); their AlleleSupport (the reference base's counts) decides the order among one-base
+// overlaps.  Leftovers past the last cleared block return to the state as candidates of the next block.
+static void span_reallocate(SpanBatch& B)
+{
+    PiscesHip* h = B.h;
+    const int32_t last_cleared = B.keys->back() * h->cfg.block_size;
+    auto ref_candidate_exists = [&](int32_t p, int32_t (&sup)[3]) {
+        // (not a gVCF: Reference candidates exist at the positions of the forced alleles only, RegionState.cs:393-396)
+        const bool forced_here = !h->cfg.include_reference_calls && h->forced_positions.count(p) != 0;
+        if (!(h->cfg.include_reference_calls || forced_here) || p < 1 || p > h->ref_len || !inside_intervals(h, p)) return false;
+        if (!in_batch(B, p)) return false;
+        const int64_t li = row_index(B, locus_index(B, p));
+        const int rb = span_atype((char)h->h_ref[(size_t)p - 1]);
+        int total = 0;
+        sup[0] = sup[1] = sup[2] = 0;
+        if (li >= 0)
+            for (int at = 0; at < PISCES_NUM_ALLELE_TYPES; at++)
+                for (int d = 0; d < 3; d++) {
+                    const int cnt = row_count(B, li, at, d);
+                    if (at == rb) sup[d] = cnt;
+                    total += cnt;
+                }
+        return h->cfg.emit_zero_coverage_refs != 0 || forced_here || total > 0;   // RegionState.cs:446
+    };
+    for (CandPtr f : B.failed)
+        for (size_t k = 0; k < f->alt.size(); k++) {
+            const int32_t p = f->position + (int32_t)k;
+            if (f->alt[k] != f->ref[k] || B.touched_refs.count(p)) continue;
+            int32_t sup[3];
+            if (!ref_candidate_exists(p, sup)) continue;
+            B.touched_refs[p] = B.arena.make(p, std::string(1, f->ref[k]), std::string(1, f->ref[k]), sup);
+        }
+    // GetAllCandidates appends the Reference candidates after the variant candidates of a block: the order only matters for
+    // ties between alleles of equal length, support and bases, which Reference candidates (base == reference) cannot have with
+    // a variant; among themselves they are in position order
+    std::vector<CandPtr> ref_originals;
+    std::vector<std::array<int32_t, 3>> ref_before;
+    for (auto& kv : B.touched_refs) {
+        B.callable_alleles.push_back(kv.second);
+        ref_originals.push_back(kv.second);
+        ref_before.push_back({kv.second->support_by_dir[0], kv.second->support_by_dir[1], kv.second->support_by_dir[2]});
+    }
+    std::vector<CandPtr> outside;
+    { HostTimer prof_r(h->prof_on ? &h->prof[11] : nullptr); mnv_reallocate_failed(B.arena, B.failed, B.callable_alleles, true, last_cleared, outside); }
+    for (CandPtr o : outside)   // source.AddCandidates(leftovers.Select(AlleleHelper.Map)) :92-93
+        if (o->category != PISCES_CAT_REFERENCE && o->position > 0) {
+            HostCandidate c = *o;
+            c.well_anchored_by_dir[0] = c.well_anchored_by_dir[1] = c.well_anchored_by_dir[2] = 0;
+            c.open_left = c.open_right = false;
+            c.stamp = next_host_stamp(h);
+            c.from_reads = false;   // (support that reallocation moved: no longer what the allele counts say)
+            add_candidate(h, c);
+        }
+    // Reference candidates keep only what reallocation added: the kernel supplies their own counts
+    for (size_t i = 0; i < ref_originals.size(); i++)
+        for (int d = 0; d < 3; d++) ref_originals[i]->support_by_dir[d] -= ref_before[i][(size_t)d];
+}
+
+// what the reallocation leaves for the final pass: GetRefSupportFromGappedMnvs :180-203 -> IAlleleSource.AddGappedMnvRefCount, and the
+// callable alleles (with a failed MNV that is a forced allele, AlleleCaller.cs:98-107)
+static void span_mnv_final_list(SpanBatch& B)
+{
+    PiscesHip* h = B.h;
+    std::vector<int32_t> gapped_now;
+    for (CandPtr a : B.callable_alleles) {
+        if (a->category != PISCES_CAT_MNV) continue;
+        const int support = cand_support(*a);
+        for (size_t k = 0; k < a->ref.size() && k < a->alt.size(); k++)
+            if (a->ref[k] == a->alt[k]) { h->gapped_mnv_ref[a->position + (int32_t)k] += support; gapped_now.push_back(a->position + (int32_t)k); }
+    }
+    // The tile kernels of this flush ran before these counts existed: the Reference allele of such a position (its support less what the
+    // gapped MNVs take, CoverageCalculator.cs:82-97) comes from the candidate kernel and replaces theirs.  (SNVs of the position are
+    // candidates of this pass anyway: an MNV spans it.)
+    std::vector<CandPtr> gapped_refs;
+    if (B.blocks_first) {
+        std::sort(gapped_now.begin(), gapped_now.end());
+        gapped_now.erase(std::unique(gapped_now.begin(), gapped_now.end()), gapped_now.end());
+        static const int32_t kNoSupport[3] = {0, 0, 0};
+        for (int32_t p : gapped_now) {
+            if (B.touched_refs.count(p)) { if (cand_support(*B.touched_refs[p]) == 0) gapped_refs.push_back(B.touched_refs[p]); continue; }
+            if (!h->cfg.include_reference_calls || p < 1 || p > h->ref_len || !in_batch(B, p)) continue;
+            B.touched_refs[p] = B.arena.make(p, std::string(1, (char)h->h_ref[(size_t)p - 1]), std::string(1, (char)h->h_ref[(size_t)p - 1]), kNoSupport);
+            gapped_refs.push_back(B.touched_refs[p]);
+        }
+    }
+    if (!h->forced.empty())
+        for (CandPtr f : B.failed)
+            if (is_forced_allele(h, *f)) B.callable_alleles.push_back(f);
+    for (CandPtr a : B.callable_alleles) {
+        if (a->category == PISCES_CAT_REFERENCE && cand_support(*a) == 0) continue;   // untouched: the tile kernels' record stands
+        B.final_list.push_back(a);
+    }
+    for (CandPtr a : gapped_refs) B.final_list.push_back(a);
+}
+
+// not a gVCF, forced alleles given: Reference candidates at the forced positions of the cleared blocks, with or without coverage
+// (RegionState.GetAllCandidates :393-450 with CreateIntervalsFromAllels); the candidate kernel makes their records from the counts
+static void span_forced_references(SpanBatch& B)
+{
+    PiscesHip* h = B.h;
+    static const int32_t kNone[3] = {0, 0, 0};
+    for (int32_t p : h->forced_positions) {
+        if (p < 1 || p > h->ref_len || !inside_intervals(h, p) || !in_batch(B, p)) continue;
+        if (B.touched_refs.count(p)) {
+            if (cand_support(*B.touched_refs[p]) != 0) continue;   // in the list already, with what reallocation added
+        } else {
+            B.touched_refs[p] = B.arena.make(p, std::string(1, (char)h->h_ref[(size_t)p - 1]), std::string(1, (char)h->h_ref[(size_t)p - 1]), kNone);
+        }
+        B.final_list.push_back(B.touched_refs[p]);
+    }
+}
+
+// the final pass's records: Reference alleles to ref_overrides, the reported alleles to recs / called (AlleleCaller.cs:109-131)
+static void span_report(SpanBatch& B, std::vector<PiscesCalledAllele>& recs, std::vector<HostCandidate>& called, int64_t* n_called,
+                        std::vector<PiscesCalledAllele>& ref_overrides)
+{
+    PiscesHip* h = B.h;
+    const bool have_forced = !h->forced.empty();
+    for (size_t i = 0; i < B.final_list.size(); i++) {
+        const HostCandidate& c = *B.final_list[i];
+        if (c.category == PISCES_CAT_REFERENCE) {   // counted as called by the tile kernels already (gVCF)
+            ref_overrides.push_back(B.raw[i]);
+            continue;
+        }
+        // a forced allele is reported whether it is callable or not; IsCallable runs once in the test for IsForcedToReport and once in
+        // the test for reporting, and counts a callable forced allele twice in TotalNumCalled
+        const bool forced = have_forced && is_forced_allele(h, c);
+        const bool reportable = B.callable[i] && inside_intervals(h, c.position);
+        if (B.callable[i] && owned(h, c.position)) (*n_called) += forced ? 2 : 1;
+        if (forced && !h->snv_walk && c.category == PISCES_CAT_SNV && reportable && !split_dirty_at(h, c.position)) {   // MNV calling off: the tile kernels report it,
+            (*n_called)--;                                                                                         // and have counted it once
             continue;
         }
         if (!reportable && !forced) continue;
-        PiscesCalledAllele r = raw[i];
+        PiscesCalledAllele r = B.raw[i];
         if (forced && !reportable) {
             // IsForcedToReport: the ForcedReport filter, and no genotyper sees the allele (:150): the genotype of a new CalledAllele
             // (CalledAllele.cs:151) and genotype q-score 0, against which AlleleCaller's LowGQ filter is taken (:166-170)
@@ -1710,24 +1744,492 @@ static int32_t call_spanning(PiscesHip* h, const std::vector<int32_t>& keys, int
             r.genotype_qscore = 0;
         }
         recs.push_back(r);
-        called.push_back(*final_list[i]);
+        called.push_back(c);
     }
-    if (rows_missing || counts_missing) return fail(h, PISCES_E_INTERNAL, "flush: a candidate's counts were not among those made for the batch");
+}
+
+// IAlleleCaller.Call for the host-found candidates of `keys` (AlleleCaller.CallForPositions :60-141): anchor-resolved counts of every
+// block a candidate touches -> collapser -> call_spanning_kernel -> callable candidates with their records.  With MNV calling on
+// the candidates include the SNVs / MNVs of the read walk: MNV candidates are processed first, the ones that are not callable go
+// through MnvReallocator on the host, leftovers past the last cleared block return to the state as candidates of the next block,
+// reference support taken by gapped MNVs is registered (it reaches the Reference records through the tile kernels, which run after
+// this), and every callable allele is processed again.  ref_overrides: Reference alleles that reallocation added support to
+// (they replace the tile kernels' Reference record of that position).
+// blocks_first: the tile kernels of this flush are enqueued already (their Reference records do not know the reference support that
+// gapped MNVs of THIS batch take: the Reference alleles of those positions come from here, as overrides), and h->fold says where their
+// folded counts lie.  The stages follow the host profile's phases (prof[1..6]; prof[11]: the reallocator).
+static int32_t call_spanning(PiscesHip* h, const std::vector<int32_t>& keys, int32_t up_to_position, std::vector<PiscesCalledAllele>& recs,
+                             std::vector<HostCandidate>& called, int64_t* n_called, int64_t* n_collapsed,
+                             std::vector<PiscesCalledAllele>& ref_overrides, bool blocks_first = false)
+{
+    recs.clear();
+    called.clear();
+    ref_overrides.clear();
+    *n_collapsed = 0;
+    const bool mnv_mode = h->cfg.call_mnvs != 0;
+    std::unique_ptr<HostTimer> prof(new HostTimer(h->prof_on ? &h->prof[1] : nullptr));
+    auto phase = [&](int i) { prof.reset(); prof.reset(new HostTimer(h->prof_on ? &h->prof[i] : nullptr)); };
+    SpanBatch B;
+    B.h = h;
+    B.keys = &keys;
+    B.up_to_position = up_to_position;
+    B.blocks_first = blocks_first;
+    span_gather_candidates(B);
+    if (!h->snv_walk) span_gather_unwalked(B);
+    if (B.work.empty() && B.unw.empty()) return PISCES_OK;
+    const std::vector<int32_t> need_pos = span_tensor_positions(B);
+    phase(2);
+    { int32_t rc = span_count_tiles(B, need_pos); if (rc) return rc; }
+    { int32_t rc = span_count_rows(B); if (rc) return rc; }
+    phase(3);
+    if (h->cfg.collapse) {
+        span_collapse(B, n_collapsed);
+        if (B.max_cleared >= 0 && B.work.empty() && B.unw.empty()) return PISCES_OK;
+    }
+    if (!B.unw.empty()) {
+        span_unwalked_snvs(B);
+        if (B.work.empty()) return PISCES_OK;
+    }
+    phase(4);
+    if (!mnv_mode) {
+        for (auto& c : B.work) B.final_list.push_back(&c);
+    } else {
+        { int32_t rc = span_mnv_pass(B); if (rc) return rc; }
+        phase(5);
+        span_sort_mnv_pass(B, n_called);
+        if (!B.failed.empty()) span_reallocate(B);
+        span_mnv_final_list(B);
+    }
+    if (!h->forced.empty() && !h->cfg.include_reference_calls) span_forced_references(B);
+    if (B.rows_missing || B.counts_missing) return fail(h, PISCES_E_INTERNAL, "flush: a candidate's counts were not among those made for the batch");
+    phase(6);
+    B.second_pass = mnv_mode;
+    { int32_t rc = span_device_pass(B, B.final_list, h->forced.empty() ? kSpanningCallableRecords : kSpanningEveryRecord); if (rc) return rc; }
+    span_report(B, recs, called, n_called, ref_overrides);
+    if (B.rows_missing || B.counts_missing) return fail(h, PISCES_E_INTERNAL, "flush: a candidate's counts were not among those made for the batch");
     return PISCES_OK;
 }
 
-int32_t pisces_hip_flush_ex(PiscesHip* h, int32_t up_to_position, PiscesCalledAllele* out, int64_t capacity, int64_t* n_out,
-                            int32_t* cand_index_out, PiscesCandidate* cand_out, int64_t cand_capacity, int64_t* n_cand,
-                            uint8_t* alleles_out, int64_t allele_capacity, int64_t* allele_bytes)
+// GetCandidatesToProcess (RegionStateManager.cs:283-334): the blocks that lie wholly at or below upTo (every block on the final flush), up
+// to the first one whose spanning alleles reach past upTo: it is held, and so is everything after it (:304-308)
+static std::vector<int32_t> select_flush_blocks(PiscesHip* h, int32_t up_to_position, bool final_flush)
 {
-    return abi_guard<int32_t>(h, [&]() -> int32_t {
-    if (!h) return PISCES_E_INVALID_ARG;
-    if (!n_out || capacity < 0 || (capacity > 0 && !out)) return fail(h, PISCES_E_INVALID_ARG, "flush: null output");
-    HostTimer timer(h->in_flush_begin ? nullptr : &h->host_time[1]);   // (flush_begin times the synchronous flush it may run itself)
-    PISCES_HIP_CHECK(h, hipSetDevice(h->device));
-    *n_out = 0;
-    if (n_cand) *n_cand = 0;
-    if (allele_bytes) *allele_bytes = 0;
+    std::vector<int32_t> keys;
+    for (auto& kv : h->blocks) {   // std::map: ascending keys
+        if (!(final_flush || (int64_t)kv.first * h->cfg.block_size <= up_to_position)) continue;
+        if (!final_flush && kv.second.max_allele_endpoint > up_to_position) break;
+        keys.push_back(kv.first);
+    }
+    return keys;
+}
+
+// Can pisces_hip_flush_begin leave the batch `keys` to the device alone?  Not when it needs the host between its device passes: host-side
+// candidates, x_spans or unwalked bases in a block; forced alleles; the per-locus genotypers; NoiseModel.Window; gapped-MNV reference counts
+// in the batch.  MNV calling on, split form: a batch without dirty loci is the tile kernels' alone (SNVs from the allele counts); off-interval
+// loci are dirty, and a store that has grown large is swept by a synchronous flush (the groups of flushed blocks leave it there).
+static bool flush_runs_async(PiscesHip* h, const std::vector<int32_t>& keys)
+{
+    if (!h->forced.empty() || germline(h) || h->cfg.noise_model == PISCES_NOISE_WINDOW) return false;
+    for (int32_t key : keys) {
+        const BlockObs& b = h->blocks.at(key);
+        if (!b.cands.empty() || !b.x_spans.empty() || !b.unwalked.empty()) return false;
+    }
+    if (h->mnv_split && (!h->intervals.empty() || h->snv_ub > (4ll << 20))) return false;
+    for (auto& kv : h->gapped_mnv_ref)
+        if (std::binary_search(keys.begin(), keys.end(), block_key(h, kv.first))) return false;
+    return true;
+}
+
+// DoneProcessing (RegionStateManager.cs:336-353) on the host and in the read store: the flushed blocks leave, with the gapped-MNV reference
+// counts of their positions, and the next batch is only built once upTo has moved past upTo's block.  (The observation log's drop is the
+// caller's: the synchronous and the asynchronous flush commit it differently.)
+static int32_t retire_flushed_blocks(PiscesHip* h, const std::vector<int32_t>& keys, int32_t up_to_position)
+{
+    for (int32_t key : keys) {
+        h->blocks.erase(key);
+        const int32_t bstart = (key - 1) * h->cfg.block_size + 1, bend = key * h->cfg.block_size;
+        for (auto it = h->gapped_mnv_ref.begin(); it != h->gapped_mnv_ref.end();)
+            it = (it->first >= bstart && it->first <= bend) ? h->gapped_mnv_ref.erase(it) : std::next(it);
+    }
+    h->last_block = nullptr;
+    { int32_t rcs = store_commit_flush(h, keys); if (rcs) return rcs; }
+    h->last_up_to_block_key = up_to_position < 0 ? -1 : block_key(h, up_to_position);
+    return PISCES_OK;
+}
+
+// ---- AlleleCaller.Call's rows of a batch (:143-177) ----------------------------------------------------------------------------------
+// The tile kernels' rows arrive in (position, ref, alt) order, one per locus and more; the candidate kernel's rows (a handful per block) go
+// in among them.  The merge is a list of events over the tile kernels' rows, each place found by bisection: a row goes in FRONT of row i
+// (a candidate row, or not a gVCF: the Reference row of a forced position that the tile kernels have no row for, a row and a call of its
+// own, AlleleCaller.IsCallable); the Reference row i goes, because a variant is reported on its position (AlleleCaller.cs:146-147); the
+// Reference row i is replaced by the one MNV reallocation added support to.  Rows between two events move in one piece.
+extern "C++" {
+static const char kBaseOfAllele[6] = {'A', 'G', 'C', 'T', 'N', 'D'};
+static std::string ref_of(const PiscesCalledAllele& r) { return std::string(1, kBaseOfAllele[PISCES_INFO_REF(r.info)]); }
+static std::string alt_of(const PiscesCalledAllele& r) { return std::string(1, kBaseOfAllele[PISCES_INFO_ALT(r.info)]); }
+static bool forced_to_report(const PiscesCalledAllele& r) { return ((r.filter_bits >> PISCES_FILTER_FORCED_REPORT) & 1u) != 0; }
+
+struct MergeRow { const PiscesCalledAllele* row; int32_t ci; const std::string* ref; const std::string* alt; };
+struct MergeEvent { size_t idx; int kind; const PiscesCalledAllele* row; int32_t ci; };   // kind 0: insert in front of idx, 1: drop idx, 2: replace idx
+
+// a tile kernel's row (one-base alleles) against a row with allele strings: true when p goes first or they are equal
+static bool point_first(const PiscesCalledAllele& p, const MergeRow& s)
+{
+    if (p.position != s.row->position) return p.position < s.row->position;
+    const char pr = kBaseOfAllele[PISCES_INFO_REF(p.info)], pa = kBaseOfAllele[PISCES_INFO_ALT(p.info)];
+    const std::string& sr = *s.ref;
+    const std::string& sa = *s.alt;
+    const int cr = sr.empty() ? 1 : (pr != sr[0] ? (pr < sr[0] ? -1 : 1) : (sr.size() > 1 ? -1 : 0));   // "X" against the string
+    if (cr != 0) return cr < 0;
+    const int ca = sa.empty() ? 1 : (pa != sa[0] ? (pa < sa[0] ? -1 : 1) : (sa.size() > 1 ? -1 : 0));
+    return ca <= 0;
+}
+static bool point_before(const PiscesCalledAllele& a, const PiscesCalledAllele& b)   // (position, ref, alt) of two tile kernels' rows
+{
+    if (a.position != b.position) return a.position < b.position;
+    const char ar = kBaseOfAllele[PISCES_INFO_REF(a.info)], br = kBaseOfAllele[PISCES_INFO_REF(b.info)];
+    if (ar != br) return ar < br;
+    return kBaseOfAllele[PISCES_INFO_ALT(a.info)] < kBaseOfAllele[PISCES_INFO_ALT(b.info)];
+}
+
+// In place, when the rows lie in the download buffer and it has room for the ones that join them: a row that comes in pushes the rows
+// behind it one place along only until the Reference row of its position goes (the usual pair of events), so nearly all of the buffer
+// stays where the kernel wrote it.  (A copy of every row was 5 of the 7 ms a flush of 230 000 loci of BASELINE config 4 spent on the host.)
+struct InPlaceWriter {
+    PiscesCalledAllele* M;
+    size_t np;
+    std::deque<PiscesCalledAllele> ahead;   // rows [cur, rp) of the input: read out of the way of the write cursor
+    size_t cur = 0, rp = 0, w = 0;          // next input row; first input row still in its place (>= cur); next output place (<= rp)
+    std::vector<std::pair<size_t, int32_t>> placed;
+    void put(const PiscesCalledAllele& row)
+    {
+        if (w == rp && rp < np) { ahead.push_back(M[rp]); rp++; }
+        M[w++] = row;
+    }
+    void emit(const PiscesCalledAllele& row, int32_t ci) { if (ci >= 0) placed.push_back({w, ci}); put(row); }
+    void skip() { if (!ahead.empty()) ahead.pop_front(); else rp++; cur++; }
+    void copy_to(size_t end)
+    {
+        while (cur < end && !ahead.empty()) {
+            const PiscesCalledAllele row = ahead.front();
+            ahead.pop_front();
+            cur++;
+            put(row);
+        }
+        if (cur < end) {   // nothing read ahead: rp == cur, w <= cur
+            const size_t n = end - cur;
+            if (w != cur) std::memmove(M + w, M + cur, n * sizeof(PiscesCalledAllele));
+            w += n;
+            cur = rp = end;
+        }
+    }
+};
+// into vectors of their own
+struct VectorWriter {
+    const PiscesCalledAllele* P;
+    std::vector<PiscesCalledAllele>& rows;
+    std::vector<int32_t>& index;
+    size_t cur = 0;
+    void emit(const PiscesCalledAllele& row, int32_t ci) { rows.push_back(row); index.push_back(ci); }
+    void skip() { cur++; }
+    void copy_to(size_t end)
+    {
+        if (end <= cur) return;
+        rows.insert(rows.end(), P + cur, P + end);
+        index.insert(index.end(), end - cur, -1);
+        cur = end;
+    }
+};
+template <class Writer>
+static void walk_events(const std::vector<MergeEvent>& evs, size_t np, Writer& w)
+{
+    for (size_t e = 0; e < evs.size(); e++) {
+        const MergeEvent& ev = evs[e];
+        w.copy_to(ev.idx);
+        if (ev.kind == 0) { w.emit(*ev.row, ev.ci); continue; }
+        if (w.cur != ev.idx) continue;   // (the row is gone already: dropped and replaced at once)
+        if (ev.kind == 2) {
+            // a Reference row that a variant of its position removes is not brought back by its replacement
+            bool dropped = false;
+            for (size_t q = e; q-- > 0 && evs[q].idx == ev.idx;) dropped = dropped || evs[q].kind == 1;
+            if (!dropped) w.emit(*ev.row, -1);
+        }
+        w.skip();
+    }
+    w.copy_to(np);
+}
+}   // extern "C++"
+
+// r.view / r.n_view: the tile kernels' rows as the last kernel left them (none: no tiles); r.cands: the candidates of span_recs.  On return
+// r holds the merged rows and their candidate index.  check_order: the rows are reworked anyway (forced alleles, the host genotyper), and
+// tile kernels' rows out of (position, ref, alt) order are stable-sorted first — as the general sort that once served them did.
+static void merge_rows(PiscesHip* h, PiscesHip::FlushResult& r, const std::vector<PiscesCalledAllele>& span_recs,
+                       const std::vector<PiscesCalledAllele>& ref_overrides, bool check_order)
+{
+    const PiscesCalledAllele* P = r.view;
+    const size_t np = r.n_view;
+    std::vector<PiscesCalledAllele> sorted;
+    if (check_order) {
+        bool in_order = true;
+        for (size_t i = 1; i < np && in_order; i++) in_order = !point_before(P[i], P[i - 1]);
+        if (!in_order) {
+            sorted.assign(P, P + np);
+            std::stable_sort(sorted.begin(), sorted.end(), point_before);
+            P = sorted.data();
+        }
+    }
+    auto first_at = [&](int32_t position) {   // first row at or behind the position
+        size_t a = 0, b = np;
+        while (a < b) { const size_t m = (a + b) >> 1; if (P[m].position < position) a = m + 1; else b = m; }
+        return a;
+    };
+    auto reference_at = [&](int32_t position) {   // the first Reference row of the position (np: none)
+        for (size_t k = first_at(position); k < np && P[k].position == position; k++)
+            if (PISCES_INFO_CATEGORY(P[k].info) == PISCES_CAT_REFERENCE) return k;
+        return np;
+    };
+    // positions whose Reference rows go: a reported variant of the candidate kernel (one that is only there because it was forced prunes
+    // nothing, AlleleCaller.cs:146), and with forced alleles given a tile kernel's variant (Reference rows then come from the candidate kernel)
+    std::vector<int32_t> drop_pos;
+    for (auto& s : span_recs)
+        if (!forced_to_report(s)) drop_pos.push_back(s.position);
+    if (!h->forced.empty())
+        for (size_t k = 0; k < np; k++)
+            if (PISCES_INFO_CATEGORY(P[k].info) != PISCES_CAT_REFERENCE && (drop_pos.empty() || drop_pos.back() != P[k].position)) drop_pos.push_back(P[k].position);
+    std::sort(drop_pos.begin(), drop_pos.end());
+    drop_pos.erase(std::unique(drop_pos.begin(), drop_pos.end()), drop_pos.end());
+
+    std::vector<MergeEvent> evs;
+    evs.reserve(span_recs.size() * 2 + ref_overrides.size());
+    std::vector<MergeRow> ins;
+    std::deque<std::string> own_alleles;   // (the strings of the Reference rows that come in)
+    for (auto& ov : ref_overrides) {
+        const size_t k = reference_at(ov.position);
+        if (k < np) { evs.push_back({k, 2, &ov, -1}); continue; }
+        if (h->cfg.include_reference_calls) continue;
+        r.called++;
+        if (std::binary_search(drop_pos.begin(), drop_pos.end(), ov.position)) continue;
+        own_alleles.push_back(ref_of(ov));
+        const std::string* ref = &own_alleles.back();
+        own_alleles.push_back(alt_of(ov));
+        ins.push_back({&ov, -1, ref, &own_alleles.back()});
+    }
+    for (size_t i = 0; i < span_recs.size(); i++) ins.push_back({&span_recs[i], (int32_t)i, &r.cands[i].ref, &r.cands[i].alt});
+    std::stable_sort(ins.begin(), ins.end(), [](const MergeRow& a, const MergeRow& b) {
+        if (a.row->position != b.row->position) return a.row->position < b.row->position;
+        if (*a.ref != *b.ref) return *a.ref < *b.ref;
+        return *a.alt < *b.alt;
+    });
+    for (auto& s : ins) {
+        size_t i = first_at(s.row->position);
+        while (i < np && point_first(P[i], s)) i++;
+        evs.push_back({i, 0, s.row, s.ci});
+    }
+    for (int32_t p : drop_pos)
+        for (size_t k = first_at(p); k < np && P[k].position == p; k++)
+            if (PISCES_INFO_CATEGORY(P[k].info) == PISCES_CAT_REFERENCE) evs.push_back({k, 1, nullptr, -1});
+    std::stable_sort(evs.begin(), evs.end(), [](const MergeEvent& a, const MergeEvent& b) { return a.idx != b.idx ? a.idx < b.idx : a.kind < b.kind; });
+
+    r.rows.clear();
+    r.index.clear();
+    const size_t room = h->h_dl_cap / sizeof(PiscesCalledAllele);
+    if ((h->merge_in_place || evs.empty()) && h->h_dl && P == (const PiscesCalledAllele*)h->h_dl + 1 && room > 0 && np + ins.size() + 1 <= room) {
+        InPlaceWriter w{(PiscesCalledAllele*)h->h_dl + 1, np};
+        w.placed.reserve(ins.size());
+        walk_events(evs, np, w);
+        r.view = w.M;
+        r.n_view = w.w;
+        r.index.assign(w.w, -1);
+        for (auto& pl : w.placed) r.index[pl.first] = pl.second;
+    } else {
+        r.rows.reserve(np + ins.size());
+        r.index.reserve(np + ins.size());
+        VectorWriter w{P, r.rows, r.index};
+        walk_events(evs, np, w);
+        r.view = nullptr;
+        r.n_view = 0;
+    }
+}
+
+// ComputeGenotypeAndFilterAllele :143-177 with DiploidThresholdingGenotyper over the merged rows, position by position: one genotype per
+// locus, alleles beyond the ploidy dropped, every kept allele gets its own diploid genotype q-score, LowGQ and MultiAllelicSite filters; the
+// device's somatic genotype fields are replaced.  (Reference rows at variant loci are gone already, rows are in (ref, alt) order.)  The rows
+// that stay move to the front; returns their number.
+static size_t genotype_rows(PiscesHip* h, PiscesCalledAllele* rows, int32_t* index, size_t n, const std::vector<HostCandidate>& cands)
+{
+    auto ref_at = [&](size_t k) { return index[k] >= 0 ? cands[(size_t)index[k]].ref : ref_of(rows[k]); };
+    auto alt_at = [&](size_t k) { return index[k] >= 0 ? cands[(size_t)index[k]].alt : alt_of(rows[k]); };
+    std::vector<DiploidAllele> at;
+    std::vector<size_t> at_row;
+    size_t out = 0;
+    for (size_t i = 0; i < n;) {
+        size_t j = i;
+        while (j < n && rows[j].position == rows[i].position) j++;
+        at.clear();
+        at_row.clear();
+        for (size_t k = i; k < j; k++) {
+            if (forced_to_report(rows[k])) continue;   // the genotyper does not see alleles that are only there because they were forced (:150)
+            DiploidAllele a;
+            a.category = PISCES_INFO_CATEGORY(rows[k].info);
+            a.ref = ref_at(k);
+            a.alt = alt_at(k);
+            a.support = rows[k].allele_support;
+            a.coverage = rows[k].total_coverage;
+            a.ref_support = rows[k].reference_support;
+            at.push_back(std::move(a));
+            at_row.push_back(k);
+        }
+        if (h->cfg.ploidy == PISCES_PLOIDY_HAPLOID)
+            (void)haploid_set_genotypes(at, h->cfg.diploid_snv_params[0], h->cfg.diploid_snv_params[1], h->cfg.min_coverage,
+                                        h->cfg.min_genotype_qscore, h->cfg.max_genotype_qscore);
+        else
+            (void)diploid_set_genotypes(at, h->cfg.diploid_snv_params, h->cfg.diploid_indel_params, h->cfg.min_coverage,
+                                        h->cfg.min_genotype_qscore, h->cfg.max_genotype_qscore);
+        const size_t first_out = out;
+        size_t ai = 0;
+        for (size_t k = i; k < j; k++) {
+            PiscesCalledAllele r = rows[k];
+            if (ai < at_row.size() && at_row[ai] == k) {
+                const DiploidAllele& a = at[ai++];
+                // an allele beyond the ploidy goes, unless it is a forced allele (:155-163)
+                if (a.prune && !(!h->forced_keys.empty() && h->forced_keys.count(forced_key(r.position, a.ref, a.alt)))) continue;
+                r.info = (uint16_t)((r.info & ~0xFu) | ((uint32_t)a.genotype & 0xFu));
+                r.genotype_qscore = a.genotype_qscore;
+                uint32_t fb = r.filter_bits & ~(1u << PISCES_FILTER_LOW_GENOTYPE_QUALITY) & 0x3FFFu;
+                if (a.multi_allelic) fb |= 1u << PISCES_FILTER_MULTI_ALLELIC_SITE;
+                if (h->cfg.low_gq_filter >= 0 && (float)a.genotype_qscore < (float)h->cfg.low_gq_filter) fb |= 1u << PISCES_FILTER_LOW_GENOTYPE_QUALITY;
+                fb |= (uint32_t)(a.phase_set_index & 3) << 14;
+                r.filter_bits = (uint16_t)fb;
+            }
+            rows[out] = r;
+            index[out] = index[k];
+            out++;
+        }
+        if (h->cfg.ploidy == PISCES_PLOIDY_DIPLOID && !h->forced.empty()) {
+            // DiploidLocusProcessor.Process (DiploidLocusProcessor.cs:13-52): a forced allele takes the genotype the other alleles of the
+            // position imply, every allele the smallest genotype q-score among those others
+            bool any_forced = false, any_other = false, is_ref = false, is_no_call = false;
+            int min_gq = 0;
+            for (size_t q = first_out; q < out; q++) {
+                const PiscesCalledAllele& r = rows[q];
+                if (forced_to_report(r)) { any_forced = true; continue; }
+                const int g = PISCES_INFO_GENOTYPE(r.info);
+                if (PISCES_INFO_CATEGORY(r.info) == PISCES_CAT_REFERENCE) is_ref = true;
+                if (g == PISCES_GT_ALT12_LIKE_NOCALL || g == PISCES_GT_ALT_LIKE_NOCALL || g == PISCES_GT_HEMI_NOCALL || g == PISCES_GT_REF_LIKE_NOCALL) is_no_call = true;
+                if (!any_other || r.genotype_qscore < min_gq) min_gq = r.genotype_qscore;
+                any_other = true;
+            }
+            if (any_forced) {
+                if (!any_other) is_no_call = true;
+                const uint32_t genotype = is_no_call ? PISCES_GT_ALT_LIKE_NOCALL : is_ref ? PISCES_GT_HOM_REF : PISCES_GT_OTHERS;
+                for (size_t q = first_out; q < out; q++) {
+                    PiscesCalledAllele& r = rows[q];
+                    if (forced_to_report(r)) r.info = (uint16_t)((r.info & ~0xFu) | genotype);
+                    r.genotype_qscore = (int16_t)(any_other ? min_gq : 0);
+                }
+            }
+        }
+        i = j;
+    }
+    return out;
+}
+
+// The flush of upTo up to the hand-out: the batch's blocks, the candidates' rows (call_spanning), the tile kernels' rows (call_blocks_enqueue),
+// the two merged, the host genotyper — into r, which stays valid (the batch made, not committed) until flush_commit.  Nothing to flush (upTo in
+// the block of the last flush): r empty and not valid.
+static int32_t flush_build(PiscesHip* h, int32_t up_to_position, PiscesHip::FlushResult& r)
+{
+    const bool final_flush = up_to_position < 0;
+    r.clear();
+    r.up_to = up_to_position;
+    add_forced_as_candidates(h, final_flush ? -1 : up_to_position);   // SmallVariantCaller.cs:101-108: before Call(upTo)
+    if (!final_flush && block_key(h, up_to_position) == h->last_up_to_block_key) return PISCES_OK;
+    r.keys = select_flush_blocks(h, up_to_position, final_flush);
+    const std::vector<int32_t>& keys = r.keys;
+    // MNV calling on, split form: the dirty loci of the batch, the SNV groups on them, the tile kernels' parameters for this flush
+    struct SplitGuard { PiscesHip* h; ~SplitGuard() { split_restore(h); } } split_guard{h};
+    { HostTimer prof_split(h->prof_on ? &h->prof[10] : nullptr); int32_t rcs = split_prepare(h, keys, final_flush ? -1 : up_to_position); if (rcs) return rcs; }
+    // The tile kernels first when they are the fused kernel over a run of whole blocks: their launch leaves the folded counts of every
+    // locus for the candidate kernel (no second walk over the reads for point alleles, MNVs and deletions), and it runs while the host
+    // collects the candidates.  Otherwise (counts in HBM, NoiseModel.Window, an interval set, an observation log) the candidates go first:
+    // with MNV calling on they register the reference support that gapped MNVs take, which the tile kernels' Reference records must see
+    // (AlleleCaller.cs:95, CoverageCalculator.cs:82-97).
+    CallBlocksInFlight st;
+    const bool blocks_first = fused_regular_applies(h, keys);
+    int32_t rc = PISCES_OK;
+    if (blocks_first) {
+        // (the folded counts only when a candidate can ask for them: 72 B a locus that an SNV-only flush need not write)
+        bool want_folded = h->mnv_split || !h->forced.empty();
+        if (!want_folded)
+            for (auto& kv : h->blocks)
+                if (!kv.second.cands.empty() || !kv.second.unwalked.empty()) { want_folded = true; break; }
+        rc = call_blocks_enqueue(h, keys, true, -1, &st, want_folded);
+        if (rc) return rc;
+    }
+    std::vector<PiscesCalledAllele> span_recs, ref_overrides;
+    rc = call_spanning(h, keys, final_flush ? -1 : up_to_position, span_recs, r.cands, &r.called, &r.collapsed, ref_overrides, blocks_first && st.active);
+    h->fold.valid = false;
+    if (rc) return rc;
+    std::unique_ptr<HostTimer> prof(new HostTimer(h->prof_on ? &h->prof[7] : nullptr));
+    // per-locus genotypers: on the device, over the tile kernels' slots, when nothing joins their rows; else the host pass over the merged rows
+    const bool device_genotyper = germline(h) && h->device_genotyper && span_recs.empty() && h->forced.empty() && ref_overrides.empty();
+    const bool host_genotyper = germline(h) && !device_genotyper;
+    if (!blocks_first) {
+        rc = call_blocks_enqueue(h, keys, true, -1, &st, false, device_genotyper);
+        if (rc) return rc;
+    }
+    if (st.active) {
+        // (with the tile kernels enqueued first the candidate passes have waited for the stream more than once since: this wait is short)
+        PISCES_TIMED_WAIT(h, hipStreamSynchronize(h->stream));
+        h->h_meta_used = 0;   // the stream is idle: nothing reads the arena any more
+#ifdef PISCES_STORE_TIMING
+        dump_tile_stamps(h);
+#endif
+        int32_t total = 0;
+        rc = call_blocks_finish(h, st, &total, &r.called, &r.kept);
+        if (rc) return rc;
+        r.dropped = st.drop_now;
+        r.view = st.hrec;   // (the pinned download buffer: valid until the next call_blocks_enqueue)
+        r.n_view = (size_t)total;
+    }
+    prof.reset();
+    prof.reset(new HostTimer(h->prof_on ? &h->prof[8] : nullptr));
+    merge_rows(h, r, span_recs, ref_overrides, host_genotyper || !h->forced.empty());
+    if (host_genotyper) {
+        const size_t n = genotype_rows(h, r.view ? r.view : r.rows.data(), r.index.data(), r.size(), r.cands);
+        if (r.view) r.n_view = n;
+        else r.rows.resize(n);
+        r.index.resize(n);
+    }
+    if (!keys.empty()) h->host_time[3] += 1.0;
+    r.valid = true;
+    return PISCES_OK;
+}
+
+// DoneProcessing of a synchronous flush once its rows are handed out: the log entries of the flushed blocks left with the tile kernels'
+// submission when there was one, and that buffer becomes the log; then the state's blocks (retire_flushed_blocks)
+static int32_t flush_commit(PiscesHip* h)
+{
+    PiscesHip::FlushResult& r = h->result;
+    if (!r.valid) return PISCES_OK;
+    if (r.dropped) {
+        commit_drop(h, r.kept);
+        r.dropped = false;
+    } else {
+        int32_t rcd = drop_blocks(h, r.keys);
+        if (rcd) return rcd;
+    }
+    { int32_t rc = retire_flushed_blocks(h, r.keys, r.up_to); if (rc) return rc; }
+    h->stats[0] += r.called;
+    h->stats[1] += r.collapsed;
+    r.valid = false;
+    return PISCES_OK;
+}
+
+// pisces_hip_flush_ex / pisces_hip_flush_view up to the hand-out: the batch of upTo in h->result — made now, or kept from the call with
+// the same upTo that reported PISCES_E_BUFFER_TOO_SMALL
+static int32_t flush_prepare(PiscesHip* h, int32_t up_to_position)
+{
     if (h->async.state != 0) return fail(h, PISCES_E_STATE, "flush: pisces_hip_flush_begin is waiting for its pisces_hip_flush_end");
     // The candidates of the last batch are waited for unless every read of it starts MORE THAN ONE position behind upTo (a read whose first
     // operation is I or D puts its candidate at position - 1: finder_walk.h, CandidateVariantFinder.cs:52-76): then none of them lies in a
@@ -1735,461 +2237,81 @@ int32_t pisces_hip_flush_ex(PiscesHip* h, int32_t up_to_position, PiscesCalledAl
     // the next stretch of reads before it calls up to their first position (SmallVariantCaller's LastClearedPosition) has the device
     // discover that stretch's candidates under this flush's host work.
     { int32_t rcd = finish_candidate_discovery(h); if (rcd) return rcd; }   // (the records of the last batch's walk go on their way before this flush's kernels)
-    if (!(up_to_position >= 0 && h->found.in_flight && h->found.min_position - 1 > up_to_position && !h->pending_valid)) { int32_t rcf = consume_found(h); if (rcf) return rcf; }
-    const bool final_flush = up_to_position < 0;
-    const bool replay = h->pending_valid && h->pending_up_to == up_to_position;
-    if (!replay) {
-        { int32_t rcp = refuse_while_batch_is_open(h, "flush (another upToPosition)"); if (rcp) return rcp; }
-        // GetCandidatesToProcess (RegionStateManager.cs:283-334): only build a batch when upTo has moved
-        // onto another block; take blocks that lie wholly at or below upTo.
-        add_forced_as_candidates(h, final_flush ? -1 : up_to_position);   // SmallVariantCaller.cs:101-108: before Call(upTo)
-        if (!final_flush && block_key(h, up_to_position) == h->last_up_to_block_key) return PISCES_OK;
-        std::vector<int32_t> keys;
-        for (auto& kv : h->blocks) {   // std::map: ascending keys
-            if (!(final_flush || (int64_t)kv.first * h->cfg.block_size <= up_to_position)) continue;
-            // a block whose spanning alleles reach past upTo is held, and so is everything after it (:304-308)
-            if (!final_flush && kv.second.max_allele_endpoint > up_to_position) break;
-            keys.push_back(kv.first);
-        }
-        int64_t called = 0;
-        std::vector<PiscesCalledAllele> point_recs, span_recs;
-        std::vector<HostCandidate> span_cands;
-        // MNV calling on, split form: the dirty loci of the batch, the SNV groups on them, the tile kernels' parameters for this flush
-        struct SplitGuard { PiscesHip* h; ~SplitGuard() { split_restore(h); } } split_guard{h};
-        { HostTimer prof_split(h->prof_on ? &h->prof[10] : nullptr); int32_t rcs = split_prepare(h, keys, final_flush ? -1 : up_to_position); if (rcs) return rcs; }
-        // host-side candidates first: with MNV calling on they register the reference support that gapped MNVs take, which the
-        // Reference records of call_blocks must see (AlleleCaller.cs:95, CoverageCalculator.cs:82-97)
-        int64_t collapsed = 0;
-        std::vector<PiscesCalledAllele> ref_overrides;
-        // The tile kernels first when they are the fused kernel over a run of whole blocks: their launch leaves the folded counts of every
-        // locus for the candidate kernel (no second walk over the reads for point alleles, MNVs and deletions), and it runs while the host
-        // collects the candidates.  Otherwise (counts in HBM, NoiseModel.Window, an interval set, an observation log) the candidates go first,
-        // as they always did: the Reference records then see what gapped MNVs take.
-        CallBlocksInFlight blocks_st;
-        const bool blocks_first = fused_regular_applies(h, keys);
-        int32_t rc = PISCES_OK;
-        if (blocks_first) {
-            // (the folded counts only when a candidate can ask for them: 72 B a locus that an SNV-only flush need not write)
-            bool want_folded = h->mnv_split || !h->forced.empty();
-            if (!want_folded)
-                for (auto& kv : h->blocks)
-                    if (!kv.second.cands.empty() || !kv.second.unwalked.empty()) { want_folded = true; break; }
-            rc = call_blocks_enqueue(h, keys, true, -1, &blocks_st, want_folded);
-            if (rc) return rc;
-        }
-        rc = call_spanning(h, keys, final_flush ? -1 : up_to_position, span_recs, span_cands, &called, &collapsed, ref_overrides, blocks_first && blocks_st.active);
-        h->fold.valid = false;
-        h->pending_collapsed = collapsed;
-        if (rc) return rc;
-        h->pending_dropped = false;
-        std::unique_ptr<HostTimer> prof(new HostTimer(h->prof_on ? &h->prof[7] : nullptr));
-        // per-locus genotypers: on the device, over the tile kernels' slots, when nothing joins their rows; else the host pass over the merged rows
-        const bool device_genotyper = germline(h) && h->device_genotyper && span_recs.empty() && h->forced.empty() && ref_overrides.empty();
-        const bool diploid = germline(h) && !device_genotyper;
-        // nothing to merge into the tile kernels' records: they go from the download buffer straight to the caller
-        const bool plain = span_recs.empty() && !diploid && h->forced.empty() && ref_overrides.empty();
-        // the tile kernels' rows are read where the last kernel left them (pinned memory) unless a per-locus genotyper or forced alleles rework them
-        const bool fast_merge = !plain && !diploid && h->forced.empty();
-        if (blocks_first) {
-            // (enqueued above; the candidate passes have waited for the stream more than once since: this wait is short)
-            if (blocks_st.active) {
-                PISCES_TIMED_WAIT(h, hipStreamSynchronize(h->stream));
-                h->h_meta_used = 0;
-#ifdef PISCES_STORE_TIMING
-                dump_tile_stamps(h);
-#endif
-                int32_t total = 0;
-                rc = call_blocks_finish(h, blocks_st, &total, &called, &h->pending_kept);
-                if (rc) return rc;
-                if (blocks_st.drop_now) h->pending_dropped = true;
-                if (plain || fast_merge) { h->pending_view = blocks_st.hrec; h->pending_view_n = (size_t)total; }
-                else point_recs.assign(blocks_st.hrec, blocks_st.hrec + total);
-            }
-        } else {
-        rc = call_blocks(h, keys, point_recs, &called, true, &h->pending_dropped, &h->pending_kept, plain || fast_merge, device_genotyper);
-        if (rc) return rc;
-        }
-        prof.reset();
-        prof.reset(new HostTimer(h->prof_on ? &h->prof[8] : nullptr));
-        if (fast_merge) {
-            // The candidate kernel's rows (a handful per block) go into the tile kernels' rows (position, ref, alt order, one per locus and
-            // more): where each belongs is found by bisection, the rows between two such places are copied in one piece.  Three kinds of
-            // places: a candidate row goes in FRONT of a row; a Reference row goes because a variant of the candidate kernel is reported on its
-            // position (AlleleCaller.cs:146-147); a Reference row is replaced by the one MNV reallocation added support to.
-            static const char kBaseF[6] = {'A', 'G', 'C', 'T', 'N', 'D'};
-            const PiscesCalledAllele* const P = h->pending_view;
-            const size_t np = h->pending_view_n;
-            auto first_at = [&](int32_t position) {   // first row at or behind the position
-                size_t a = 0, b = np;
-                while (a < b) { const size_t m = (a + b) >> 1; if (P[m].position < position) a = m + 1; else b = m; }
-                return a;
-            };
-            struct SRow { const PiscesCalledAllele* r; int32_t ci; const std::string* ref; const std::string* alt; };
-            std::vector<SRow> rows;
-            rows.reserve(span_recs.size());
-            for (size_t i = 0; i < span_recs.size(); i++) rows.push_back({&span_recs[i], (int32_t)i, &span_cands[i].ref, &span_cands[i].alt});
-            std::stable_sort(rows.begin(), rows.end(), [](const SRow& a, const SRow& b) {
-                if (a.r->position != b.r->position) return a.r->position < b.r->position;
-                if (*a.ref != *b.ref) return *a.ref < *b.ref;
-                return *a.alt < *b.alt;
-            });
-            auto point_first = [&](const PiscesCalledAllele& p, const SRow& sr) {   // true: p goes before sr (or they are equal): one-base alleles against strings
-                const char pr = kBaseF[PISCES_INFO_REF(p.info)], pa = kBaseF[PISCES_INFO_ALT(p.info)];
-                const int cr = sr.ref->empty() ? 1 : (pr != (*sr.ref)[0] ? (pr < (*sr.ref)[0] ? -1 : 1) : (sr.ref->size() > 1 ? -1 : 0));
-                if (cr != 0) return cr < 0;
-                const int ca = sr.alt->empty() ? 1 : (pa != (*sr.alt)[0] ? (pa < (*sr.alt)[0] ? -1 : 1) : (sr.alt->size() > 1 ? -1 : 0));
-                return ca <= 0;
-            };
-            struct Ev { size_t idx; int kind; const PiscesCalledAllele* row; int32_t ci; };   // kind 0: insert in front of idx, 1: drop idx, 2: replace idx
-            std::vector<Ev> evs;
-            evs.reserve(rows.size() * 2 + ref_overrides.size());
-            int32_t last_dropped = -1;
-            for (auto& sr : rows) {
-                size_t i = first_at(sr.r->position);
-                while (i < np && P[i].position == sr.r->position && point_first(P[i], sr)) i++;
-                evs.push_back({i, 0, sr.r, sr.ci});
-                const bool forced_row = ((sr.r->filter_bits >> PISCES_FILTER_FORCED_REPORT) & 1u) != 0;
-                if (!forced_row && sr.r->position != last_dropped) {
-                    last_dropped = sr.r->position;
-                    for (size_t k = first_at(sr.r->position); k < np && P[k].position == sr.r->position; k++)
-                        if (PISCES_INFO_CATEGORY(P[k].info) == PISCES_CAT_REFERENCE) evs.push_back({k, 1, nullptr, -1});
-                }
-            }
-            for (auto& ov : ref_overrides)
-                for (size_t k = first_at(ov.position); k < np && P[k].position == ov.position; k++)
-                    if (PISCES_INFO_CATEGORY(P[k].info) == PISCES_CAT_REFERENCE) { evs.push_back({k, 2, &ov, -1}); break; }
-            std::stable_sort(evs.begin(), evs.end(), [](const Ev& a, const Ev& b) { return a.idx != b.idx ? a.idx < b.idx : a.kind < b.kind; });
-            h->pending.clear();
-            h->pending_cand_index.clear();
-            // In place when the rows lie in the download buffer and it has room for the ones that join them: a row that comes in pushes the
-            // rows behind it one place along only until the Reference row of its position goes (the usual pair of events), so nearly all
-            // of the buffer stays where the kernel wrote it.  (A copy of every row into h->pending was 5 of the 7 ms a flush of 230 000
-            // loci of BASELINE config 4 spent on the host.)
-            const size_t room = h->h_dl_cap / sizeof(PiscesCalledAllele);
-            if (h->merge_in_place && h->h_dl && P == (const PiscesCalledAllele*)h->h_dl + 1 && room > 0 && np + rows.size() + 1 <= room) {
-                PiscesCalledAllele* const M = (PiscesCalledAllele*)h->h_dl + 1;
-                std::deque<PiscesCalledAllele> ahead;   // rows [cur, rp) of the input: read out of the way of the write cursor
-                size_t cur = 0, rp = 0, w = 0;          // next input row; first input row still in its place (>= cur); next output place (<= rp)
-                std::vector<std::pair<size_t, int32_t>> placed;
-                placed.reserve(rows.size());
-                auto emit = [&](const PiscesCalledAllele& row) {
-                    if (w == rp && rp < np) { ahead.push_back(M[rp]); rp++; }
-                    M[w++] = row;
-                };
-                auto skip_one = [&]() { if (!ahead.empty()) ahead.pop_front(); else rp++; cur++; };
-                auto copy_to = [&](size_t end) {
-                    while (cur < end && !ahead.empty()) {
-                        const PiscesCalledAllele row = ahead.front();
-                        ahead.pop_front();
-                        cur++;
-                        emit(row);
-                    }
-                    if (cur < end) {   // nothing read ahead: rp == cur, w <= cur
-                        const size_t n = end - cur;
-                        if (w != cur) std::memmove(M + w, M + cur, n * sizeof(PiscesCalledAllele));
-                        w += n;
-                        cur = rp = end;
-                    }
-                };
-                for (size_t e = 0; e < evs.size(); e++) {
-                    const Ev& ev = evs[e];
-                    copy_to(ev.idx);
-                    if (ev.kind == 0) { placed.push_back({w, ev.ci}); emit(*ev.row); continue; }
-                    if (cur != ev.idx) continue;                       // (the row is gone already: dropped and replaced at once)
-                    if (ev.kind == 2) {
-                        bool dropped = false;
-                        for (size_t q = e; q-- > 0 && evs[q].idx == ev.idx;) dropped = dropped || evs[q].kind == 1;
-                        if (!dropped) emit(*ev.row);
-                    }
-                    skip_one();
-                }
-                copy_to(np);
-                h->pending_view = M;
-                h->pending_view_n = w;
-                h->pending_cand_index.assign(w, -1);
-                for (auto& pl : placed) h->pending_cand_index[pl.first] = pl.second;
-                h->pending_cands = span_cands;
-            } else {
-            h->pending.reserve(np + rows.size());
-            h->pending_cand_index.reserve(np + rows.size());
-            size_t cur = 0;
-            auto copy_to = [&](size_t end) {
-                if (end > cur) {
-                    h->pending.insert(h->pending.end(), P + cur, P + end);
-                    h->pending_cand_index.insert(h->pending_cand_index.end(), end - cur, -1);
-                    cur = end;
-                }
-            };
-            for (size_t e = 0; e < evs.size(); e++) {
-                const Ev& ev = evs[e];
-                copy_to(ev.idx);
-                if (ev.kind == 0) { h->pending.push_back(*ev.row); h->pending_cand_index.push_back(ev.ci); continue; }
-                if (cur != ev.idx) continue;                       // (the row is gone already: dropped and replaced at once)
-                if (ev.kind == 2) {
-                    // a Reference row that a variant of its position removes is not brought back by its replacement
-                    bool dropped = false;
-                    for (size_t q = e; q-- > 0 && evs[q].idx == ev.idx;) dropped = dropped || evs[q].kind == 1;
-                    if (!dropped) { h->pending.push_back(*ev.row); h->pending_cand_index.push_back(-1); }
-                }
-                cur = ev.idx + 1;
-            }
-            copy_to(np);
-            h->pending_view = nullptr;
-            h->pending_view_n = 0;
-            h->pending_cands = span_cands;
-            }
-        } else {
-        if (!ref_overrides.empty()) {   // Reference alleles that MNV reallocation added support to
-            std::map<int32_t, const PiscesCalledAllele*> by_pos;
-            for (auto& r : ref_overrides) by_pos[r.position] = &r;
-            for (auto& r : point_recs) {
-                if (PISCES_INFO_CATEGORY(r.info) != PISCES_CAT_REFERENCE) continue;
-                auto it = by_pos.find(r.position);
-                if (it != by_pos.end()) { r = *it->second; by_pos.erase(it); }
-            }
-            // not a gVCF: the Reference alleles at forced positions have no tile-kernel record to replace; they are rows (and calls,
-            // AlleleCaller.IsCallable) of their own
-            if (!h->cfg.include_reference_calls)
-                for (auto& kv : by_pos) { point_recs.push_back(*kv.second); called++; }
-        }
-        // per locus: drop the Reference row when a variant is reported there (AlleleCaller.cs:146-147), then order by
-        // position, reference allele, alternate allele (:172-176; ordinal order of upper-case ASCII allele strings)
-        h->pending.clear();
-        h->pending_cand_index.clear();
-        h->pending_cands = span_cands;
-        if (plain) {
-            h->pending_cand_index.assign(h->pending_view_n, -1);
-        } else if (span_recs.empty() && !diploid && h->forced.empty()) {
-            h->pending = std::move(point_recs);
-            h->pending_cand_index.assign(h->pending.size(), -1);
-        } else {
-            struct Row { const PiscesCalledAllele* r; int32_t ci; std::string ref, alt; };
-            static const char kBase[6] = {'A', 'G', 'C', 'T', 'N', 'D'};
-            std::vector<Row> rows;
-            // (a variant that is only there because it was forced prunes nothing: AlleleCaller.cs:146)
-            auto forced_to_report = [](const PiscesCalledAllele& r) { return ((r.filter_bits >> PISCES_FILTER_FORCED_REPORT) & 1u) != 0; };
-            std::vector<int32_t> variant_pos;
-            for (auto& r : span_recs)
-                if (!forced_to_report(r)) variant_pos.push_back(r.position);
-            if (!h->forced.empty())   // forced alleles given: Reference rows can come from the candidate kernel, beside the tile kernels' SNV rows
-                for (auto& r : point_recs)
-                    if (PISCES_INFO_CATEGORY(r.info) != PISCES_CAT_REFERENCE) variant_pos.push_back(r.position);
-            std::sort(variant_pos.begin(), variant_pos.end());
-            auto row_before = [](const Row& a, const Row& b) {
-                if (a.r->position != b.r->position) return a.r->position < b.r->position;
-                if (a.ref != b.ref) return a.ref < b.ref;
-                return a.alt < b.alt;
-            };
-            if (!diploid) {
-                // The tile kernels' rows arrive in (position, ref, alt) order; only the candidate kernel's rows (a handful per block) need
-                // sorting, and the two runs are merged — rows of the tile kernels first among equals, as a stable sort of the rows in
-                // that order leaves them.  (Every row used to go through the sort with its two allele strings: 118 of the 151 ms of the
-                // flushes of a 900 000-locus contig of BASELINE config 4.)
-                for (size_t i = 0; i < span_recs.size(); i++) rows.push_back({&span_recs[i], (int32_t)i, span_cands[i].ref, span_cands[i].alt});
-                std::stable_sort(rows.begin(), rows.end(), row_before);
-                h->pending.reserve(point_recs.size() + rows.size());
-                h->pending_cand_index.reserve(point_recs.size() + rows.size());
-                // a tile kernel's row against a candidate row: its alleles are one base each
-                auto point_first = [&](const PiscesCalledAllele& p, const Row& sr) {   // true: p goes before sr (or they are equal)
-                    if (p.position != sr.r->position) return p.position < sr.r->position;
-                    const char pr = kBase[PISCES_INFO_REF(p.info)], pa = kBase[PISCES_INFO_ALT(p.info)];
-                    const int cr = sr.ref.empty() ? 1 : (pr != sr.ref[0] ? (pr < sr.ref[0] ? -1 : 1) : (sr.ref.size() > 1 ? -1 : 0));   // "X" against sr.ref
-                    if (cr != 0) return cr < 0;
-                    const int ca = sr.alt.empty() ? 1 : (pa != sr.alt[0] ? (pa < sr.alt[0] ? -1 : 1) : (sr.alt.size() > 1 ? -1 : 0));
-                    return ca <= 0;
-                };
-                size_t si = 0;
-                bool point_sorted = true;
-                for (size_t i = 1; i < point_recs.size() && point_sorted; i++) point_sorted = point_recs[i - 1].position <= point_recs[i].position;
-                if (point_sorted) {
-                    for (auto& r : point_recs) {
-                        const bool is_ref = PISCES_INFO_CATEGORY(r.info) == PISCES_CAT_REFERENCE;
-                        if (is_ref && std::binary_search(variant_pos.begin(), variant_pos.end(), r.position)) continue;
-                        while (si < rows.size() && !point_first(r, rows[si])) { h->pending.push_back(*rows[si].r); h->pending_cand_index.push_back(rows[si].ci); si++; }
-                        h->pending.push_back(r);
-                        h->pending_cand_index.push_back(-1);
-                    }
-                    for (; si < rows.size(); si++) { h->pending.push_back(*rows[si].r); h->pending_cand_index.push_back(rows[si].ci); }
-                } else {
-                    // (rows of the tile kernels that are not in position order — not something a flush produces: the general sort)
-                    std::vector<Row> all;
-                    for (auto& r : point_recs) {
-                        const bool is_ref = PISCES_INFO_CATEGORY(r.info) == PISCES_CAT_REFERENCE;
-                        if (is_ref && std::binary_search(variant_pos.begin(), variant_pos.end(), r.position)) continue;
-                        all.push_back({&r, -1, std::string(1, kBase[PISCES_INFO_REF(r.info)]), std::string(1, kBase[PISCES_INFO_ALT(r.info)])});
-                    }
-                    for (auto& sr : rows) all.push_back(sr);
-                    std::stable_sort(all.begin(), all.end(), row_before);
-                    for (auto& row : all) { h->pending.push_back(*row.r); h->pending_cand_index.push_back(row.ci); }
-                }
-            } else {
-            for (auto& r : point_recs) {
-                const bool is_ref = PISCES_INFO_CATEGORY(r.info) == PISCES_CAT_REFERENCE;
-                if (is_ref && std::binary_search(variant_pos.begin(), variant_pos.end(), r.position)) continue;
-                rows.push_back({&r, -1, std::string(1, kBase[PISCES_INFO_REF(r.info)]), std::string(1, kBase[PISCES_INFO_ALT(r.info)])});
-            }
-            for (size_t i = 0; i < span_recs.size(); i++) rows.push_back({&span_recs[i], (int32_t)i, span_cands[i].ref, span_cands[i].alt});
-            std::stable_sort(rows.begin(), rows.end(), row_before);
-            {
-                // ComputeGenotypeAndFilterAllele :143-177 with DiploidThresholdingGenotyper: one genotype per locus, alleles beyond the
-                // ploidy dropped, every kept allele gets its own diploid genotype q-score, LowGQ and MultiAllelicSite filters; the
-                // device's somatic genotype fields are replaced.  (Reference rows at variant loci are gone already, rows are in
-                // (ref, alt) order.)
-                std::vector<DiploidAllele> at;
-                std::vector<size_t> at_row;
-                for (size_t i = 0; i < rows.size();) {
-                    size_t j = i;
-                    while (j < rows.size() && rows[j].r->position == rows[i].r->position) j++;
-                    at.clear();
-                    at_row.clear();
-                    for (size_t k = i; k < j; k++) {
-                        if (forced_to_report(*rows[k].r)) continue;   // the genotyper does not see alleles that are only there because they were forced (:150)
-                        DiploidAllele a;
-                        a.category = PISCES_INFO_CATEGORY(rows[k].r->info);
-                        a.ref = rows[k].ref;
-                        a.alt = rows[k].alt;
-                        a.support = rows[k].r->allele_support;
-                        a.coverage = rows[k].r->total_coverage;
-                        a.ref_support = rows[k].r->reference_support;
-                        at.push_back(std::move(a));
-                        at_row.push_back(k);
-                    }
-                    if (h->cfg.ploidy == PISCES_PLOIDY_HAPLOID)
-                        (void)haploid_set_genotypes(at, h->cfg.diploid_snv_params[0], h->cfg.diploid_snv_params[1], h->cfg.min_coverage,
-                                                    h->cfg.min_genotype_qscore, h->cfg.max_genotype_qscore);
-                    else
-                        (void)diploid_set_genotypes(at, h->cfg.diploid_snv_params, h->cfg.diploid_indel_params, h->cfg.min_coverage,
-                                                    h->cfg.min_genotype_qscore, h->cfg.max_genotype_qscore);
-                    const size_t first_out = h->pending.size();
-                    size_t ai = 0;
-                    for (size_t k = i; k < j; k++) {
-                        PiscesCalledAllele r = *rows[k].r;
-                        if (ai < at_row.size() && at_row[ai] == k) {
-                            const DiploidAllele& a = at[ai++];
-                            // an allele beyond the ploidy goes, unless it is a forced allele (:155-163)
-                            if (a.prune && !(!h->forced_keys.empty() && h->forced_keys.count(forced_key(r.position, rows[k].ref, rows[k].alt)))) continue;
-                            r.info = (uint16_t)((r.info & ~0xFu) | ((uint32_t)a.genotype & 0xFu));
-                            r.genotype_qscore = a.genotype_qscore;
-                            uint32_t fb = r.filter_bits & ~(1u << PISCES_FILTER_LOW_GENOTYPE_QUALITY) & 0x3FFFu;
-                            if (a.multi_allelic) fb |= 1u << PISCES_FILTER_MULTI_ALLELIC_SITE;
-                            if (h->cfg.low_gq_filter >= 0 && (float)a.genotype_qscore < (float)h->cfg.low_gq_filter) fb |= 1u << PISCES_FILTER_LOW_GENOTYPE_QUALITY;
-                            fb |= (uint32_t)(a.phase_set_index & 3) << 14;
-                            r.filter_bits = (uint16_t)fb;
-                        }
-                        h->pending.push_back(r);
-                        h->pending_cand_index.push_back(rows[k].ci);
-                    }
-                    if (h->cfg.ploidy == PISCES_PLOIDY_DIPLOID && !h->forced.empty()) {
-                        // DiploidLocusProcessor.Process (DiploidLocusProcessor.cs:13-52): a forced allele takes the genotype the other alleles of
-                        // the position imply, every allele the smallest genotype q-score among those others
-                        bool any_forced = false, any_other = false, is_ref = false, is_no_call = false;
-                        int min_gq = 0;
-                        for (size_t q = first_out; q < h->pending.size(); q++) {
-                            const PiscesCalledAllele& r = h->pending[q];
-                            if (forced_to_report(r)) { any_forced = true; continue; }
-                            const int g = PISCES_INFO_GENOTYPE(r.info);
-                            if (PISCES_INFO_CATEGORY(r.info) == PISCES_CAT_REFERENCE) is_ref = true;
-                            if (g == PISCES_GT_ALT12_LIKE_NOCALL || g == PISCES_GT_ALT_LIKE_NOCALL || g == PISCES_GT_HEMI_NOCALL || g == PISCES_GT_REF_LIKE_NOCALL) is_no_call = true;
-                            if (!any_other || r.genotype_qscore < min_gq) min_gq = r.genotype_qscore;
-                            any_other = true;
-                        }
-                        if (any_forced) {
-                            if (!any_other) is_no_call = true;
-                            const uint32_t genotype = is_no_call ? PISCES_GT_ALT_LIKE_NOCALL : is_ref ? PISCES_GT_HOM_REF : PISCES_GT_OTHERS;
-                            for (size_t q = first_out; q < h->pending.size(); q++) {
-                                PiscesCalledAllele& r = h->pending[q];
-                                if (forced_to_report(r)) r.info = (uint16_t)((r.info & ~0xFu) | genotype);
-                                r.genotype_qscore = (int16_t)(any_other ? min_gq : 0);
-                            }
-                        }
-                    }
-                    i = j;
-                }
-            }
-            }
-        }
-        }   // (!fast_merge)
-        if (!keys.empty()) h->host_time[3] += 1.0;
-        h->pending_keys = keys;
-        h->pending_called = called;
-        h->pending_up_to = up_to_position;
-        h->pending_valid = true;
-    }
+    if (!(up_to_position >= 0 && h->found.in_flight && h->found.min_position - 1 > up_to_position && !h->result.valid)) { int32_t rcf = consume_found(h); if (rcf) return rcf; }
+    if (h->result.valid && h->result.up_to == up_to_position) return PISCES_OK;
+    { int32_t rcp = refuse_while_batch_is_open(h, "flush (another upToPosition)"); if (rcp) return rcp; }
+    return flush_build(h, up_to_position, h->result);
+}
+
+static int64_t allele_bytes_of(const std::vector<HostCandidate>& cands)
+{
+    int64_t bytes = 0;
+    for (auto& c : cands) bytes += (int64_t)(c.ref.size() + c.alt.size());
+    return bytes;
+}
+
+// pisces_hip_flush_view / pisces_hip_flush_end_view: where h->result's rows lie (its candidates exported next to them)
+static void flush_view_out(PiscesHip* h, const PiscesCalledAllele** rows, int64_t* n_rows, const int32_t** cand_index, const PiscesCandidate** cands,
+                           int64_t* n_cand, const uint8_t** alleles, int64_t* allele_bytes)
+{
+    PiscesHip::FlushResult& r = h->result;
+    const size_t n = r.size();
+    r.exported.resize(r.cands.size());
+    r.alleles.resize((size_t)allele_bytes_of(r.cands));
+    (void)export_candidates(r.cands, r.exported.data(), (int64_t)r.exported.size(), r.alleles.data(), (int64_t)r.alleles.size(), nullptr);
+    *rows = n ? r.data() : nullptr;
+    *n_rows = (int64_t)n;
+    // a batch the device called alone has no index (every row is a Reference or SNV row): NULL then
+    if (cand_index) *cand_index = n && r.index.size() == n ? r.index.data() : nullptr;
+    if (cands) *cands = r.exported.empty() ? nullptr : r.exported.data();
+    if (n_cand) *n_cand = (int64_t)r.exported.size();
+    if (alleles) *alleles = r.alleles.empty() ? nullptr : r.alleles.data();
+    if (allele_bytes) *allele_bytes = (int64_t)r.alleles.size();
+}
+
+static int32_t flush_to_arrays(PiscesHip* h, int32_t up_to_position, PiscesCalledAllele* out, int64_t capacity, int64_t* n_out,
+                               int32_t* cand_index_out, PiscesCandidate* cand_out, int64_t cand_capacity, int64_t* n_cand,
+                               uint8_t* alleles_out, int64_t allele_capacity, int64_t* allele_bytes)
+{
+    if (!h) return PISCES_E_INVALID_ARG;
+    if (!n_out || capacity < 0 || (capacity > 0 && !out)) return fail(h, PISCES_E_INVALID_ARG, "flush: null output");
+    HostTimer timer(&h->host_time[1]);
+    PISCES_HIP_CHECK(h, hipSetDevice(h->device));
+    *n_out = 0;
+    if (n_cand) *n_cand = 0;
+    if (allele_bytes) *allele_bytes = 0;
+    { int32_t rc = flush_prepare(h, up_to_position); if (rc) return rc; }
+    const PiscesHip::FlushResult& r = h->result;
     HostTimer prof_out(h->prof_on ? &h->prof[9] : nullptr);
-    int64_t pool_bytes = 0;
-    for (auto& c : h->pending_cands) pool_bytes += (int64_t)(c.ref.size() + c.alt.size());
-    if (n_cand) *n_cand = (int64_t)h->pending_cands.size();
+    const int64_t pool_bytes = allele_bytes_of(r.cands);
+    if (n_cand) *n_cand = (int64_t)r.cands.size();
     if (allele_bytes) *allele_bytes = pool_bytes;
-    const bool cand_too_small = cand_out && ((int64_t)h->pending_cands.size() > cand_capacity || (alleles_out && pool_bytes > allele_capacity));
-    const PiscesCalledAllele* pending_data = h->pending_view ? h->pending_view : h->pending.data();
-    const size_t pending_n = h->pending_view ? h->pending_view_n : h->pending.size();
-    auto& W = h->view;
-    if (W.wanted) {
-        // pisces_hip_flush_view: the rows are handed out where they lie — the pinned download buffer as the kernels wrote it, or the
-        // merged rows, which then move into a vector that lives until the next flush
-        if (!h->pending_view) { W.rows.swap(h->pending); pending_data = W.rows.data(); }
-        W.index.swap(h->pending_cand_index);
-        W.cands.resize(h->pending_cands.size());
-        W.alleles.resize((size_t)pool_bytes);
-        cand_out = W.cands.data();
-        alleles_out = W.alleles.data();
-        W.data = pending_data;
-        W.n = pending_n;
-    } else {
-    if ((int64_t)pending_n > capacity || cand_too_small) {
-        *n_out = (int64_t)pending_n;
+    const bool cand_too_small = cand_out && ((int64_t)r.cands.size() > cand_capacity || (alleles_out && pool_bytes > allele_capacity));
+    const size_t n = r.size();
+    if ((int64_t)n > capacity || cand_too_small) {
+        *n_out = (int64_t)n;
         return fail(h, PISCES_E_BUFFER_TOO_SMALL, "flush: output buffer too small");
     }
-    if (pending_n) std::memcpy(out, pending_data, pending_n * sizeof(PiscesCalledAllele));
-    if (cand_index_out && pending_n) std::memcpy(cand_index_out, h->pending_cand_index.data(), pending_n * sizeof(int32_t));
-    }
-    if (cand_out) {
-        int64_t off = 0;
-        for (size_t i = 0; i < h->pending_cands.size(); i++) {
-            const HostCandidate& c = h->pending_cands[i];
-            PiscesCandidate& o = cand_out[i];
-            std::memset(&o, 0, sizeof(o));
-            o.position = c.position; o.category = c.category;
-            o.ref_len = (int32_t)c.ref.size(); o.alt_len = (int32_t)c.alt.size();
-            for (int d = 0; d < 3; d++) { o.support_by_dir[d] = c.support_by_dir[d]; o.well_anchored_by_dir[d] = c.well_anchored_by_dir[d]; }
-            o.open_left = c.open_left; o.open_right = c.open_right;
-            o.allele_offset = off;
-            if (alleles_out) {
-                std::memcpy(alleles_out + off, c.ref.data(), c.ref.size());
-                std::memcpy(alleles_out + off + c.ref.size(), c.alt.data(), c.alt.size());
-            }
-            off += (int64_t)(c.ref.size() + c.alt.size());
-        }
-    }
-    *n_out = (int64_t)pending_n;
-    // DoneProcessing (RegionStateManager.cs:336-353): the log entries of the flushed blocks left with call_blocks' submission when
-    // there was one; what remains is to make that buffer the log
-    if (h->pending_dropped) {
-        commit_drop(h, h->pending_kept);
-        h->pending_dropped = false;
-    } else {
-        int32_t rcd = drop_blocks(h, h->pending_keys);
-        if (rcd) return rcd;
-    }
-    for (int32_t key : h->pending_keys) {
-        h->blocks.erase(key);
-        const int32_t bstart = (key - 1) * h->cfg.block_size + 1, bend = key * h->cfg.block_size;
-        for (auto it = h->gapped_mnv_ref.begin(); it != h->gapped_mnv_ref.end();)
-            it = (it->first >= bstart && it->first <= bend) ? h->gapped_mnv_ref.erase(it) : std::next(it);
-    }
-    h->last_block = nullptr;
-    { int32_t rcs = store_commit_flush(h, h->pending_keys); if (rcs) return rcs; }
-    h->stats[0] += h->pending_called;
-    h->stats[1] += h->pending_collapsed;
-    h->last_up_to_block_key = final_flush ? -1 : block_key(h, up_to_position);
-    h->pending_valid = false;
-    h->pending_view = nullptr;
-    h->pending_view_n = 0;
-    h->pending.clear();
-    h->pending_cand_index.clear();
-    h->pending_cands.clear();
-    h->pending_keys.clear();
-    return PISCES_OK;
+    if (n) std::memcpy(out, r.data(), n * sizeof(PiscesCalledAllele));
+    if (cand_index_out && n) std::memcpy(cand_index_out, r.index.data(), n * sizeof(int32_t));
+    if (cand_out) (void)export_candidates(r.cands, cand_out, cand_capacity, alleles_out, allele_capacity, nullptr);
+    *n_out = (int64_t)n;
+    return flush_commit(h);
+}
+
+int32_t pisces_hip_flush_ex(PiscesHip* h, int32_t up_to_position, PiscesCalledAllele* out, int64_t capacity, int64_t* n_out,
+                            int32_t* cand_index_out, PiscesCandidate* cand_out, int64_t cand_capacity, int64_t* n_cand,
+                            uint8_t* alleles_out, int64_t allele_capacity, int64_t* allele_bytes)
+{
+    return abi_guard<int32_t>(h, [&]() -> int32_t {
+    return flush_to_arrays(h, up_to_position, out, capacity, n_out, cand_index_out, cand_out, cand_capacity, n_cand, alleles_out, allele_capacity, allele_bytes);
+    });
+}
+
+int32_t pisces_hip_flush(PiscesHip* h, int32_t up_to_position, PiscesCalledAllele* out, int64_t capacity, int64_t* n_out)
+{
+    return abi_guard<int32_t>(h, [&]() -> int32_t {
+    return flush_to_arrays(h, up_to_position, out, capacity, n_out, nullptr, nullptr, 0, nullptr, nullptr, 0, nullptr);
     });
 }
 
@@ -2203,70 +2325,13 @@ int32_t pisces_hip_flush_view(PiscesHip* h, int32_t up_to_position, const Pisces
     if (!h) return PISCES_E_INVALID_ARG;
     if (!rows || !n_rows) return fail(h, PISCES_E_INVALID_ARG, "flush_view: null output");
     *rows = nullptr; *n_rows = 0;
-    auto& W = h->view;
-    struct Wanted { bool& f; explicit Wanted(bool& x) : f(x) { f = true; } ~Wanted() { f = false; } } wanted(W.wanted);
-    W.data = nullptr; W.n = 0;
-    int64_t n = 0, nc = 0, nb = 0;
-    PiscesCandidate none;   // (a non-null candidate output makes the flush fill W.cands / W.alleles)
-    const int32_t rc = pisces_hip_flush_ex(h, up_to_position, nullptr, 0, &n, nullptr, &none, 0, &nc, nullptr, 0, &nb);
-    if (rc) return rc;
-    *rows = W.data;
-    *n_rows = (int64_t)W.n;
-    // a batch the device called alone has no index (every row is a Reference or SNV row): NULL then
-    if (cand_index) *cand_index = W.index.size() == W.n && W.n ? W.index.data() : nullptr;
-    if (cands) *cands = W.cands.empty() ? nullptr : W.cands.data();
-    if (n_cand) *n_cand = (int64_t)W.cands.size();
-    if (alleles) *alleles = W.alleles.empty() ? nullptr : W.alleles.data();
-    if (allele_bytes) *allele_bytes = (int64_t)W.alleles.size();
+    HostTimer timer(&h->host_time[1]);
+    PISCES_HIP_CHECK(h, hipSetDevice(h->device));
+    { int32_t rc = flush_prepare(h, up_to_position); if (rc) return rc; }
+    HostTimer prof_out(h->prof_on ? &h->prof[9] : nullptr);
+    { int32_t rc = flush_commit(h); if (rc) return rc; }
+    flush_view_out(h, rows, n_rows, cand_index, cands, n_cand, alleles, allele_bytes);
     return PISCES_OK;
-    });
-}
-
-// pisces_hip_flush_end the same way: the rows where pisces_hip_flush_begin's work left them
-int32_t pisces_hip_flush_end_view(PiscesHip* h, const PiscesCalledAllele** rows, int64_t* n_rows, const int32_t** cand_index, const PiscesCandidate** cands,
-                                  int64_t* n_cand, const uint8_t** alleles, int64_t* allele_bytes)
-{
-    return abi_guard<int32_t>(h, [&]() -> int32_t {
-    if (!h) return PISCES_E_INVALID_ARG;
-    if (!rows || !n_rows) return fail(h, PISCES_E_INVALID_ARG, "flush_end_view: null output");
-    *rows = nullptr; *n_rows = 0;
-    // (every optional output is defined on every successful return, as pisces_hip_flush_view leaves them)
-    if (cand_index) *cand_index = nullptr;
-    if (cands) *cands = nullptr;
-    if (n_cand) *n_cand = 0;
-    if (alleles) *alleles = nullptr;
-    if (allele_bytes) *allele_bytes = 0;
-    auto& A = h->async;
-    if (A.state == 0) return fail(h, PISCES_E_STATE, "flush_end_view: no pisces_hip_flush_begin before it");
-    if (A.state == 1) {   // wait as pisces_hip_flush_end does: a call with no room for rows completes the flush and reports the count
-        int64_t need = 0;
-        const int32_t rc = pisces_hip_flush_end(h, nullptr, 0, &need);
-        if (rc == PISCES_OK) return PISCES_OK;   // no rows at all
-        if (rc != PISCES_E_BUFFER_TOO_SMALL) return rc;
-        h->err.clear();   // (the probe's "buffer too small" is not an error of this call)
-    }
-    *rows = A.data;
-    *n_rows = (int64_t)A.n;
-    // (a flush that ran inside flush_begin, with host-side candidates: its index, candidates and allele strings are kept with its rows)
-    const bool with_cands = A.n && A.data == A.owned.data();
-    if (cand_index) *cand_index = with_cands ? A.owned_index.data() : nullptr;
-    if (cands) *cands = A.n_cands ? A.owned_cands.data() : nullptr;
-    if (n_cand) *n_cand = (int64_t)A.n_cands;
-    if (alleles) *alleles = A.n_allele_bytes ? A.owned_alleles.data() : nullptr;
-    if (allele_bytes) *allele_bytes = (int64_t)A.n_allele_bytes;
-    A.state = 0;
-    A.data = nullptr;
-    A.n = 0;
-    A.n_cands = 0;
-    A.n_allele_bytes = 0;
-    return PISCES_OK;
-    });
-}
-
-int32_t pisces_hip_flush(PiscesHip* h, int32_t up_to_position, PiscesCalledAllele* out, int64_t capacity, int64_t* n_out)
-{
-    return abi_guard<int32_t>(h, [&]() -> int32_t {
-    return pisces_hip_flush_ex(h, up_to_position, out, capacity, n_out, nullptr, nullptr, 0, nullptr, nullptr, 0, nullptr);
     });
 }
 
@@ -2276,67 +2341,34 @@ int32_t pisces_hip_flush(PiscesHip* h, int32_t up_to_position, PiscesCalledAllel
 // and hands the alleles over.  Between the two the caller may add the next reads (pisces_hip_stage_reads / pisces_hip_add_reads /
 // pisces_hip_add_observations / pisces_hip_add_decoded_reads): the compaction's entry count, which the host has not seen yet, is
 // replaced by a bound -- the compacted log is made that long, holes behind the kept entries -- so appending needs nothing from the
-// device.  A batch that needs the host between its device passes (host-side candidates: insertions, deletions, MNVs; forced alleles;
-// the per-locus genotypers; NoiseModel.Window; gapped-MNV reference counts) is flushed synchronously inside begin, and end returns it.
+// device.  A batch that needs the host between its device passes (flush_runs_async) is flushed synchronously inside begin, and end
+// returns it.
 int32_t pisces_hip_flush_begin(PiscesHip* h, int32_t up_to_position)
 {
     return abi_guard<int32_t>(h, [&]() -> int32_t {
     if (!h) return PISCES_E_INVALID_ARG;
     if (h->async.state != 0) return fail(h, PISCES_E_STATE, "flush_begin: the flush before this one has not been taken (pisces_hip_flush_end)");
     HostTimer timer(&h->host_time[1]);
-    struct InBegin { bool& f; explicit InBegin(bool& x) : f(x) { f = true; } ~InBegin() { f = false; } } in_begin(h->in_flush_begin);
     { int32_t rcp = refuse_while_batch_is_open(h, "flush_begin"); if (rcp) return rcp; }
     PISCES_HIP_CHECK(h, hipSetDevice(h->device));
     { int32_t rcd = finish_candidate_discovery(h); if (rcd) return rcd; }
     if (!(up_to_position >= 0 && h->found.in_flight && h->found.min_position - 1 > up_to_position)) { int32_t rcf = consume_found(h); if (rcf) return rcf; }
     const bool final_flush = up_to_position < 0;
     auto& A = h->async;
-    // the batch GetCandidatesToProcess would build (as pisces_hip_flush_ex)
-    std::vector<int32_t> keys;
     const bool same_block = !final_flush && block_key(h, up_to_position) == h->last_up_to_block_key;
-    bool plain = h->forced.empty() && h->cfg.ploidy != PISCES_PLOIDY_DIPLOID && h->cfg.ploidy != PISCES_PLOIDY_HAPLOID &&
-                 h->cfg.noise_model != PISCES_NOISE_WINDOW;
-    if (!same_block)
-        for (auto& kv : h->blocks) {
-            if (!(final_flush || (int64_t)kv.first * h->cfg.block_size <= up_to_position)) continue;
-            if (!final_flush && kv.second.max_allele_endpoint > up_to_position) break;
-            keys.push_back(kv.first);
-            if (!kv.second.cands.empty() || !kv.second.x_spans.empty() || !kv.second.unwalked.empty()) plain = false;
-        }
-    // MNV calling on, split form: a batch without dirty loci is the tile kernels' alone (SNVs from the allele counts); off-interval loci are
-    // dirty, and a store that has grown large is swept by a synchronous flush (the groups of flushed blocks leave it there)
-    if (h->mnv_split && (!h->intervals.empty() || h->snv_ub > (4ll << 20))) plain = false;
-    for (auto& kv : h->gapped_mnv_ref)
-        if (std::binary_search(keys.begin(), keys.end(), block_key(h, kv.first))) { plain = false; break; }
-    if (!plain) {
-        // the synchronous flush, its alleles kept for pisces_hip_flush_end
-        // (with the candidates of its insertion / deletion / MNV rows and their allele strings, for pisces_hip_flush_end_ex)
-        A.owned.resize(std::max<size_t>(A.owned.size(), 1024));
-        A.owned_index.resize(A.owned.size());
-        A.owned_cands.resize(std::max<size_t>(A.owned_cands.size(), 64));
-        A.owned_alleles.resize(std::max<size_t>(A.owned_alleles.size(), 4096));
-        for (;;) {
-            int64_t n = 0, nc = 0, nb = 0;
-            const int32_t rc = pisces_hip_flush_ex(h, up_to_position, A.owned.data(), (int64_t)A.owned.size(), &n, A.owned_index.data(), A.owned_cands.data(),
-                                                   (int64_t)A.owned_cands.size(), &nc, A.owned_alleles.data(), (int64_t)A.owned_alleles.size(), &nb);
-            if (rc == PISCES_E_BUFFER_TOO_SMALL) {
-                if ((size_t)n > A.owned.size()) { A.owned.resize((size_t)n); A.owned_index.resize((size_t)n); }
-                if ((size_t)nc > A.owned_cands.size()) A.owned_cands.resize((size_t)nc);
-                if ((size_t)nb > A.owned_alleles.size()) A.owned_alleles.resize((size_t)nb);
-                continue;
-            }
-            if (rc) return rc;
-            A.data = A.owned.data();
-            A.n = (size_t)n;
-            A.n_cands = (size_t)nc;
-            A.n_allele_bytes = (size_t)nb;
-            break;
-        }
+    std::vector<int32_t> keys;
+    if (!same_block) keys = select_flush_blocks(h, up_to_position, final_flush);
+    if (!flush_runs_async(h, keys)) {
+        // the synchronous flush, its rows (with the candidates of its insertion / deletion / MNV rows) kept in h->result for pisces_hip_flush_end
+        { int32_t rc = flush_build(h, up_to_position, h->result); if (rc) return rc; }
+        HostTimer prof_out(h->prof_on ? &h->prof[9] : nullptr);
+        { int32_t rc = flush_commit(h); if (rc) return rc; }
         A.state = 2;
         return PISCES_OK;
     }
     if (!A.done) PISCES_HIP_CHECK(h, hipEventCreateWithFlags(&A.done, hipEventDisableTiming));
-    if (same_block) { A.data = nullptr; A.n = 0; A.state = 2; return PISCES_OK; }
+    h->result.clear();
+    if (same_block) { A.state = 2; return PISCES_OK; }
     // what the compacted log can hold at most: the entries that are not known holes
     const int64_t bound = std::max<int64_t>(0, h->log_ub - h->log_known_holes);
     CallBlocksInFlight st;
@@ -2356,38 +2388,43 @@ int32_t pisces_hip_flush_begin(PiscesHip* h, int32_t up_to_position)
         int32_t rcd = drop_blocks(h, keys);
         if (rcd) return rcd;
     }
-    for (int32_t key : keys) {
-        h->blocks.erase(key);
-        const int32_t bstart = (key - 1) * h->cfg.block_size + 1, bend = key * h->cfg.block_size;
-        for (auto it = h->gapped_mnv_ref.begin(); it != h->gapped_mnv_ref.end();)
-            it = (it->first >= bstart && it->first <= bend) ? h->gapped_mnv_ref.erase(it) : std::next(it);
-    }
-    h->last_block = nullptr;
-    { int32_t rcs = store_commit_flush(h, keys); if (rcs) return rcs; }
-    h->last_up_to_block_key = final_flush ? -1 : block_key(h, up_to_position);
+    { int32_t rcr = retire_flushed_blocks(h, keys, up_to_position); if (rcr) return rcr; }
     A.dropped = st.active && st.drop_now;
     A.bound = bound;
     A.hdr = st.hdr;
     A.hrec = st.hrec;
     A.spec = st.spec;
-    A.data = nullptr;
-    A.n = 0;
     A.state = st.active ? 1 : 2;
     return PISCES_OK;
     });
 }
 
-int32_t pisces_hip_flush_end(PiscesHip* h, PiscesCalledAllele* out, int64_t capacity, int64_t* n_out)
+// pisces_hip_flush_end*: once the device is done, the rows of the batch flush_begin left in flight go to h->result
+static int32_t flush_end_wait(PiscesHip* h)
 {
-    return pisces_hip_flush_end_ex(h, out, capacity, n_out, nullptr, nullptr, 0, nullptr, nullptr, 0, nullptr);
+    auto& A = h->async;
+    if (A.state != 1) return PISCES_OK;
+    PISCES_TIMED_WAIT(h, hipEventSynchronize(A.done));
+    h->h_meta_used = 0;   // (only a flush uploads through the arena, and this one's uploads lie before the event)
+    CallBlocksInFlight st;
+    st.active = true; st.drop_now = A.dropped; st.hdr = A.hdr; st.hrec = A.hrec; st.spec = A.spec;
+    int32_t total = 0;
+    int64_t called = 0;
+    unsigned long long kept = 0;
+    int32_t rc = call_blocks_finish(h, st, &total, &called, &kept);
+    if (rc) return rc;
+    // the holes the drop left are the bound minus what it kept; entries appended since lie behind the bound
+    if (A.dropped) h->log_known_holes = A.bound - (int64_t)kept;
+    h->stats[0] += called;
+    h->result.view = A.hrec;
+    h->result.n_view = (size_t)total;
+    A.state = 2;
+    return PISCES_OK;
 }
 
-// flush_end with what pisces_hip_flush_ex returns beside the records: the candidate of every insertion / deletion / MNV row and the
-// allele strings.  A flush that ran on the device alone has none (every row is a Reference or SNV row: cand_index -1).
-int32_t pisces_hip_flush_end_ex(PiscesHip* h, PiscesCalledAllele* out, int64_t capacity, int64_t* n_out, int32_t* cand_index_out, PiscesCandidate* cand_out,
-                                int64_t cand_capacity, int64_t* n_cand, uint8_t* alleles_out, int64_t allele_capacity, int64_t* allele_bytes)
+static int32_t flush_end_to_arrays(PiscesHip* h, PiscesCalledAllele* out, int64_t capacity, int64_t* n_out, int32_t* cand_index_out, PiscesCandidate* cand_out,
+                                   int64_t cand_capacity, int64_t* n_cand, uint8_t* alleles_out, int64_t allele_capacity, int64_t* allele_bytes)
 {
-    return abi_guard<int32_t>(h, [&]() -> int32_t {
     if (!h) return PISCES_E_INVALID_ARG;
     if (!n_out || capacity < 0 || (capacity > 0 && !out)) return fail(h, PISCES_E_INVALID_ARG, "flush_end: null output");
     if (cand_capacity < 0 || allele_capacity < 0 || (cand_capacity > 0 && !cand_out) || (allele_capacity > 0 && !alleles_out))
@@ -2399,84 +2436,110 @@ int32_t pisces_hip_flush_end_ex(PiscesHip* h, PiscesCalledAllele* out, int64_t c
     if (A.state == 0) return fail(h, PISCES_E_STATE, "flush_end: no pisces_hip_flush_begin before it");
     HostTimer timer(&h->host_time[1]);
     PISCES_HIP_CHECK(h, hipSetDevice(h->device));
-    if (A.state == 1) {
-        PISCES_TIMED_WAIT(h, hipEventSynchronize(A.done));
-        h->h_meta_used = 0;   // (only a flush uploads through the arena, and this one's uploads lie before the event)
-        CallBlocksInFlight st;
-        st.active = true; st.drop_now = A.dropped; st.hdr = A.hdr; st.hrec = A.hrec; st.spec = A.spec;
-        int32_t total = 0;
-        int64_t called = 0;
-        unsigned long long kept = 0;
-        int32_t rc = call_blocks_finish(h, st, &total, &called, &kept);
-        if (rc) return rc;
-        // the holes the drop left are the bound minus what it kept; entries appended since lie behind the bound
-        if (A.dropped) h->log_known_holes = A.bound - (int64_t)kept;
-        h->stats[0] += called;
-        A.data = A.hrec;
-        A.n = (size_t)total;
-        A.state = 2;
-    }
+    { int32_t rc = flush_end_wait(h); if (rc) return rc; }
+    const PiscesHip::FlushResult& r = h->result;
+    const size_t n = r.size();
+    const int64_t pool_bytes = allele_bytes_of(r.cands);
     const bool want_cands = cand_out || alleles_out || n_cand || allele_bytes;
-    if ((int64_t)A.n > capacity || (want_cands && ((int64_t)A.n_cands > cand_capacity || (int64_t)A.n_allele_bytes > allele_capacity))) {
-        *n_out = (int64_t)A.n;
-        if (n_cand) *n_cand = (int64_t)A.n_cands;
-        if (allele_bytes) *allele_bytes = (int64_t)A.n_allele_bytes;
+    if ((int64_t)n > capacity || (want_cands && ((int64_t)r.cands.size() > cand_capacity || pool_bytes > allele_capacity))) {
+        *n_out = (int64_t)n;
+        if (n_cand) *n_cand = (int64_t)r.cands.size();
+        if (allele_bytes) *allele_bytes = pool_bytes;
         return fail(h, PISCES_E_BUFFER_TOO_SMALL, "flush_end: output buffer too small");
     }
-    if (A.n) std::memcpy(out, A.data, A.n * sizeof(PiscesCalledAllele));
-    if (cand_index_out) {
-        if (A.n_cands || A.data == A.owned.data()) { if (A.n) std::memcpy(cand_index_out, A.owned_index.data(), A.n * sizeof(int32_t)); }
-        else std::fill(cand_index_out, cand_index_out + A.n, -1);
+    if (n) std::memcpy(out, r.data(), n * sizeof(PiscesCalledAllele));
+    if (cand_index_out) {   // (a batch the device called alone has no index: every row -1)
+        if (r.index.size() == n) { if (n) std::memcpy(cand_index_out, r.index.data(), n * sizeof(int32_t)); }
+        else std::fill(cand_index_out, cand_index_out + n, -1);
     }
     if (want_cands) {
-        if (A.n_cands) std::memcpy(cand_out, A.owned_cands.data(), A.n_cands * sizeof(PiscesCandidate));
-        if (A.n_allele_bytes) std::memcpy(alleles_out, A.owned_alleles.data(), A.n_allele_bytes);
-        if (n_cand) *n_cand = (int64_t)A.n_cands;
-        if (allele_bytes) *allele_bytes = (int64_t)A.n_allele_bytes;
+        (void)export_candidates(r.cands, cand_out, cand_capacity, alleles_out, allele_capacity, nullptr);
+        if (n_cand) *n_cand = (int64_t)r.cands.size();
+        if (allele_bytes) *allele_bytes = pool_bytes;
     }
-    *n_out = (int64_t)A.n;
+    *n_out = (int64_t)n;
     A.state = 0;
-    A.data = nullptr;
-    A.n = 0;
-    A.n_cands = 0;
-    A.n_allele_bytes = 0;
+    return PISCES_OK;
+}
+
+int32_t pisces_hip_flush_end(PiscesHip* h, PiscesCalledAllele* out, int64_t capacity, int64_t* n_out)
+{
+    return abi_guard<int32_t>(h, [&]() -> int32_t {
+    return flush_end_to_arrays(h, out, capacity, n_out, nullptr, nullptr, 0, nullptr, nullptr, 0, nullptr);
+    });
+}
+
+// flush_end with what pisces_hip_flush_ex returns beside the records: the candidate of every insertion / deletion / MNV row and the
+// allele strings.  A flush that ran on the device alone has none (every row is a Reference or SNV row: cand_index -1).
+int32_t pisces_hip_flush_end_ex(PiscesHip* h, PiscesCalledAllele* out, int64_t capacity, int64_t* n_out, int32_t* cand_index_out, PiscesCandidate* cand_out,
+                                int64_t cand_capacity, int64_t* n_cand, uint8_t* alleles_out, int64_t allele_capacity, int64_t* allele_bytes)
+{
+    return abi_guard<int32_t>(h, [&]() -> int32_t {
+    return flush_end_to_arrays(h, out, capacity, n_out, cand_index_out, cand_out, cand_capacity, n_cand, alleles_out, allele_capacity, allele_bytes);
+    });
+}
+
+// pisces_hip_flush_end the same way: the rows where pisces_hip_flush_begin's work left them
+int32_t pisces_hip_flush_end_view(PiscesHip* h, const PiscesCalledAllele** rows, int64_t* n_rows, const int32_t** cand_index, const PiscesCandidate** cands,
+                                  int64_t* n_cand, const uint8_t** alleles, int64_t* allele_bytes)
+{
+    return abi_guard<int32_t>(h, [&]() -> int32_t {
+    if (!h) return PISCES_E_INVALID_ARG;
+    if (!rows || !n_rows) return fail(h, PISCES_E_INVALID_ARG, "flush_end_view: null output");
+    *rows = nullptr; *n_rows = 0;
+    // (every optional output is defined on every successful return, as pisces_hip_flush_view leaves them)
+    if (cand_index) *cand_index = nullptr;
+    if (cands) *cands = nullptr;
+    if (n_cand) *n_cand = 0;
+    if (alleles) *alleles = nullptr;
+    if (allele_bytes) *allele_bytes = 0;
+    auto& A = h->async;
+    if (A.state == 0) return fail(h, PISCES_E_STATE, "flush_end_view: no pisces_hip_flush_begin before it");
+    HostTimer timer(&h->host_time[1]);
+    PISCES_HIP_CHECK(h, hipSetDevice(h->device));
+    { int32_t rc = flush_end_wait(h); if (rc) return rc; }
+    flush_view_out(h, rows, n_rows, cand_index, cands, n_cand, alleles, allele_bytes);
+    A.state = 0;
     return PISCES_OK;
     });
 }
 
-int32_t pisces_hip_get_counts(PiscesHip* h, int32_t start_position, int32_t n, int32_t* out)
+// pisces_hip_get_counts / pisces_hip_get_base_quality_sums: the cells of [start_position, start_position + n) accumulated on the device
+// (with the base-quality sums: `sums`), served over the whole block grid, not the interval-clipped tiles
+static int32_t read_cells(PiscesHip* h, const char* what, int32_t start_position, int32_t n, void* out, bool sums)
 {
-    return abi_guard<int32_t>(h, [&]() -> int32_t {
     if (!h) return PISCES_E_INVALID_ARG;
-    if (n < 0 || (n > 0 && !out)) return fail(h, PISCES_E_INVALID_ARG, "get_counts: null output");
+    if (n < 0 || (n > 0 && !out)) return fail(h, PISCES_E_INVALID_ARG, std::string(what) + ": null output");
     if (start_position <= 0) return fail(h, PISCES_E_INVALID_ARG, "Position must be greater than 0.");
     PISCES_HIP_CHECK(h, hipSetDevice(h->device));
-    std::memset(out, 0, (size_t)n * PISCES_COUNTS_PER_LOCUS * sizeof(int32_t));
+    const size_t row = PISCES_COUNTS_PER_LOCUS * (sums ? sizeof(double) : sizeof(int32_t));
+    std::memset(out, 0, (size_t)n * row);
     if (n == 0) return PISCES_OK;
     std::vector<int32_t> keys;
     for (int32_t k = block_key(h, start_position); k <= block_key(h, start_position + n - 1); k++)
         if (h->blocks.count(k)) keys.push_back(k);
     if (keys.empty()) return PISCES_OK;
-    // counts are served over the whole block grid, not the interval-clipped tiles
     std::vector<PiscesTile> tiles;
     int32_t rc = bucket_blocks(h, keys, false, tiles);
     if (rc) return rc;
     const int32_t n_tiles = (int32_t)tiles.size();
-    const size_t nc = (size_t)n_tiles * kTile * PISCES_COUNTS_PER_LOCUS;
-    PISCES_HIP_CHECK(h, accumulate_tiles(h, h->stream, h->d_tuples.p, h->d_tiles.p, n_tiles, false, true));
-    std::vector<int32_t> host(nc);
-    PISCES_HIP_CHECK(h, hipMemcpyAsync(host.data(), h->d_counts.p, nc * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    const size_t bytes = (size_t)n_tiles * kTile * row;
+    PISCES_HIP_CHECK(h, accumulate_tiles(h, h->stream, h->d_tuples.p, h->d_tiles.p, n_tiles, sums, true));   // (any handle can serve the sums, not only NoiseModel.Window)
+    std::vector<uint8_t> host(bytes);
+    PISCES_HIP_CHECK(h, hipMemcpyAsync(host.data(), sums ? (const void*)h->d_sumq.p : (const void*)h->d_counts.p, bytes, hipMemcpyDeviceToHost, h->stream));
     PISCES_HIP_CHECK(h, hipStreamSynchronize(h->stream));
     for (int32_t t = 0; t < n_tiles; t++)
         for (int32_t l = 0; l < tiles[(size_t)t].n_loci; l++) {
             int32_t p = tiles[(size_t)t].start_position + l;
             if (p < start_position || p >= start_position + n) continue;
-            std::memcpy(out + (size_t)(p - start_position) * PISCES_COUNTS_PER_LOCUS,
-                        host.data() + ((size_t)t * kTile + (size_t)l) * PISCES_COUNTS_PER_LOCUS,
-                        PISCES_COUNTS_PER_LOCUS * sizeof(int32_t));
+            std::memcpy((uint8_t*)out + (size_t)(p - start_position) * row, host.data() + ((size_t)t * kTile + (size_t)l) * row, row);
         }
     return PISCES_OK;
-    });
+}
+
+int32_t pisces_hip_get_counts(PiscesHip* h, int32_t start_position, int32_t n, int32_t* out)
+{
+    return abi_guard<int32_t>(h, [&]() -> int32_t { return read_cells(h, "get_counts", start_position, n, out, false); });
 }
 
 // IAlleleSource.GetSumOfAlleleBaseQualities (RegionState._sumOfAlleleBaseQualities, RegionState.cs:61,233-239): the cells of
@@ -2485,35 +2548,7 @@ int32_t pisces_hip_get_counts(PiscesHip* h, int32_t start_position, int32_t n, i
 // the true sum rounded once, the same bits from run to run; the reference adds doubles in read order, equal to rounding.
 int32_t pisces_hip_get_base_quality_sums(PiscesHip* h, int32_t start_position, int32_t n, double* out)
 {
-    return abi_guard<int32_t>(h, [&]() -> int32_t {
-    if (!h) return PISCES_E_INVALID_ARG;
-    if (n < 0 || (n > 0 && !out)) return fail(h, PISCES_E_INVALID_ARG, "get_base_quality_sums: null output");
-    if (start_position <= 0) return fail(h, PISCES_E_INVALID_ARG, "Position must be greater than 0.");
-    PISCES_HIP_CHECK(h, hipSetDevice(h->device));
-    std::memset(out, 0, (size_t)n * PISCES_COUNTS_PER_LOCUS * sizeof(double));
-    if (n == 0) return PISCES_OK;
-    std::vector<int32_t> keys;
-    for (int32_t k = block_key(h, start_position); k <= block_key(h, start_position + n - 1); k++)
-        if (h->blocks.count(k)) keys.push_back(k);
-    if (keys.empty()) return PISCES_OK;
-    std::vector<PiscesTile> tiles;
-    int32_t rc = bucket_blocks(h, keys, false, tiles);
-    if (rc) return rc;
-    const int32_t n_tiles = (int32_t)tiles.size();
-    const size_t nc = (size_t)n_tiles * kTile * PISCES_COUNTS_PER_LOCUS;
-    PISCES_HIP_CHECK(h, accumulate_tiles(h, h->stream, h->d_tuples.p, h->d_tiles.p, n_tiles, true, true));   // (any handle can serve the sums, not only NoiseModel.Window)
-    std::vector<double> host(nc);
-    PISCES_HIP_CHECK(h, hipMemcpyAsync(host.data(), h->d_sumq.p, nc * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    PISCES_HIP_CHECK(h, hipStreamSynchronize(h->stream));
-    for (int32_t t = 0; t < n_tiles; t++)
-        for (int32_t l = 0; l < tiles[(size_t)t].n_loci; l++) {
-            int32_t p = tiles[(size_t)t].start_position + l;
-            if (p < start_position || p >= start_position + n) continue;
-            std::memcpy(out + (size_t)(p - start_position) * PISCES_COUNTS_PER_LOCUS,
-                        host.data() + ((size_t)t * kTile + (size_t)l) * PISCES_COUNTS_PER_LOCUS, PISCES_COUNTS_PER_LOCUS * sizeof(double));
-        }
-    return PISCES_OK;
-    });
+    return abi_guard<int32_t>(h, [&]() -> int32_t { return read_cells(h, "get_base_quality_sums", start_position, n, out, true); });
 }
 
 // IAlleleSource.GetGappedMnvRefCount (RegionStateManager.cs: the lookup AddGappedMnvRefCount fills)
@@ -2595,26 +2630,13 @@ int32_t pisces_hip_get_candidates(PiscesHip* h, int32_t up_to_position, PiscesCa
         for (auto& kv : merged_blocks)
             std::stable_sort(kv.second.begin(), kv.second.end(), [](const HostCandidate& x, const HostCandidate& y) { return x.stamp < y.stamp; });
     }
-    int64_t n = 0, bytes = 0;
+    std::vector<HostCandidate> listed;
     for (auto& kv : h->blocks)
-        for (auto& c : (merged_blocks.count(kv.first) ? merged_blocks[kv.first] : kv.second.cands)) {
-            if (up_to_position >= 0 && c.position > up_to_position) continue;
-            if (out && n < capacity && (!alleles || bytes + (int64_t)(c.ref.size() + c.alt.size()) <= allele_capacity)) {
-                PiscesCandidate& o = out[n];
-                std::memset(&o, 0, sizeof(o));
-                o.position = c.position; o.category = c.category;
-                o.ref_len = (int32_t)c.ref.size(); o.alt_len = (int32_t)c.alt.size();
-                for (int d = 0; d < 3; d++) { o.support_by_dir[d] = c.support_by_dir[d]; o.well_anchored_by_dir[d] = c.well_anchored_by_dir[d]; }
-                o.open_left = c.open_left; o.open_right = c.open_right;
-                o.allele_offset = bytes;
-                if (alleles) {
-                    std::memcpy(alleles + bytes, c.ref.data(), c.ref.size());
-                    std::memcpy(alleles + bytes + c.ref.size(), c.alt.data(), c.alt.size());
-                }
-            }
-            n++;
-            bytes += (int64_t)(c.ref.size() + c.alt.size());
-        }
+        for (auto& c : (merged_blocks.count(kv.first) ? merged_blocks[kv.first] : kv.second.cands))
+            if (up_to_position < 0 || c.position <= up_to_position) listed.push_back(c);
+    int64_t bytes = 0;
+    (void)export_candidates(listed, out, out ? capacity : 0, alleles, allele_capacity, &bytes);
+    const int64_t n = (int64_t)listed.size();
     *n_out = n;
     if (allele_bytes) *allele_bytes = bytes;
     if (out && (n > capacity || (alleles && bytes > allele_capacity))) return fail(h, PISCES_E_BUFFER_TOO_SMALL, "get_candidates: buffer too small");

@@ -2326,6 +2326,32 @@ def test_flush_views_hand_out_the_rows_the_copying_flushes_return(torch_cuda):
         assert rc == _abi.E_STATE        # no flush_begin before it
 
 
+@pytest.mark.gpu
+def test_flush_view_in_the_same_block_hands_out_nothing(torch_cuda):
+    """pisces_hip_flush_view with upTo still in the block of the last flush builds no batch: no rows, and no candidates or allele
+    strings either (not those of the flush before it)."""
+    import ctypes as C
+    from pisces_amd import _native, engine
+    rng = np.random.default_rng(2)
+    refb = bytes(rng.choice(list(b"ACGT"), 2600).astype(np.uint8))
+    reads = []
+    for i in range(90):
+        s = 900 + (i % 7) * 3
+        if i % 3 == 0:
+            reads.append({"pos": s, "cigar": [("M", 60), ("D", 4), ("M", 60)], "seq": (refb[s - 1:s + 59] + refb[s + 63:s + 123]).decode(), "quals": [37] * 120, "reverse": bool(i % 2)})
+        else:
+            reads.append({"pos": s, "cigar": [("M", 124)], "seq": refb[s - 1:s + 123].decode(), "quals": [37] * 124, "reverse": bool(i % 2)})
+    with engine.HipVariantCaller(_abi.default_config()) as c:
+        c.SetReference(refb)
+        c.AddAlleleCounts(reads)
+        rows, n, idx, cands, nc, pool, nb = C.c_void_p(), C.c_int64(0), C.c_void_p(), C.c_void_p(), C.c_int64(0), C.c_void_p(), C.c_int64(0)
+        rc = _native.lib.pisces_hip_flush_view(c._h, 2500, C.byref(rows), C.byref(n), C.byref(idx), C.byref(cands), C.byref(nc), C.byref(pool), C.byref(nb))
+        assert rc == 0 and n.value > 0 and nc.value >= 1 and nb.value > 0       # blocks 1 and 2, with the deletion
+        rc = _native.lib.pisces_hip_flush_view(c._h, 2600, C.byref(rows), C.byref(n), C.byref(idx), C.byref(cands), C.byref(nc), C.byref(pool), C.byref(nb))
+        assert rc == 0 and n.value == 0 and nc.value == 0 and nb.value == 0
+        assert not rows.value and not idx.value and not cands.value and not pool.value
+
+
 def test_summary_reduce_through_the_c_abi_on_two_devices(torch_cuda):
     """pisces_hip_comm_init / pisces_hip_reduce_summary with one process per GPU (RCCL over xGMI, bound by the library): two ranks on two
     devices must both get the sums of what they handed in.  Skipped on a one-GPU box — RCCL refuses two ranks on one device — so that the
