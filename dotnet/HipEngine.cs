@@ -63,12 +63,13 @@ namespace Pisces.Hip
             c.Collapse = o.Collapse ? 1 : 0; c.CollapseFreqThreshold = o.CollapseFreqThreshold; c.CollapseFreqRatioThreshold = o.CollapseFreqRatioThreshold;
             c.CallMnvs = o.CallMNVs ? 1 : 0; c.MaxMnvLength = o.MaxSizeMNV; c.MaxGapBetweenMnv = o.MaxGapBetweenMNV;
             c.NoiseModel = v.NoiseModel == NoiseModel.Window ? 1 : 0;
-            c.Ploidy = v.PloidyModel == PloidyModel.DiploidByThresholding ? 1 : v.PloidyModel == PloidyModel.Haploid ? 2 : 0;
+            c.Ploidy = v.PloidyModel == PloidyModel.DiploidByThresholding ? 1 : v.PloidyModel == PloidyModel.Haploid ? 2 : v.PloidyModel == PloidyModel.DiploidByAdaptiveGT ? 3 : 0;
             var snv = v.DiploidSNVThresholdingParameters; var indel = v.DiploidINDELThresholdingParameters;
             c.DiploidSnvMinorVF = snv.MinorVF; c.DiploidSnvMajorVF = snv.MajorVF; c.DiploidSnvSumVF = snv.SumVFforMultiAllelicSite;
             c.DiploidIndelMinorVF = indel.MinorVF; c.DiploidIndelMajorVF = indel.MajorVF; c.DiploidIndelSumVF = indel.SumVFforMultiAllelicSite;
             // MinFrequency / VariantFreqFilter come from the genotyper (Factory.cs:160,167; IGenotypeCalculator.MinVarFrequency[Filter])
-            float minVarFrequency = c.Ploidy == 0 ? v.MinimumFrequency : snv.MinorVF;
+            // (DiploidAdaptiveGenotyper never sets MinVarFrequency: VariantCallerConfig.MinFrequency is 0 with DiploidByAdaptiveGT, Factory.cs:128-147)
+            float minVarFrequency = c.Ploidy == 0 ? v.MinimumFrequency : c.Ploidy == 3 ? 0f : snv.MinorVF;
             c.MinFrequency = minVarFrequency;
             c.VariantFreqFilter = Math.Max(v.MinimumFrequencyFilter, minVarFrequency);   // SetMinFreqFilter
             c.GenotypeMinFreqFilter = c.VariantFreqFilter;
@@ -80,6 +81,22 @@ namespace Pisces.Hip
             _cfg = cfg;
             var c = cfg;
             NativeMethods.Check(IntPtr.Zero, NativeMethods.pisces_hip_create(ref c, device, out _h));
+        }
+
+        /// PloidyModel.DiploidByAdaptiveGT: VariantCallingParameters.AdaptiveGenotypingParameters to the handle (the defaults are the library's too)
+        public unsafe void SetAdaptiveGenotypingParameters(AdaptiveGenotypingParameters a)
+        {
+            if (_cfg.Ploidy != 3) return;
+            PiscesAdaptiveParams p;
+            NativeMethods.Check(_h, NativeMethods.pisces_hip_adaptive_default_params(out p));
+            for (int i = 0; i < 3; i++)
+            {
+                p.SnvModel[i] = a.SnvModel[i]; p.IndelModel[i] = a.IndelModel[i];
+                p.SnvPrior[i] = a.SnvPrior[i]; p.IndelPrior[i] = a.IndelPrior[i];
+            }
+            p.SumVfForMultiAllelicSite = a.SumVFforMultiAllelicSite;
+            p.MaxGenotypePosteriors = a.MaxGenotypePosteriors;
+            NativeMethods.Check(_h, NativeMethods.pisces_hip_set_adaptive_params(_h, ref p));
         }
 
         public void SetIntervals(ChrIntervalSet set)
@@ -190,7 +207,7 @@ namespace Pisces.Hip
             if (HeldBack(upToPosition)) return new SortedList<int, List<CalledAllele>>();
             PiscesCalledAllele* rows; int* idx; PiscesCandidate* cands; byte* pool; long n, nc, nb;
             NativeMethods.Check(_h, NativeMethods.pisces_hip_flush_view(_h, upToPosition ?? -1, out rows, out n, out idx, out cands, out nc, out pool, out nb));
-            return ToCalledAlleles(chr, rows, n, idx, cands, pool);
+            return ToCalledAlleles(chr, rows, n, idx, cands, pool, PosteriorsOfLastFlush(n));
         }
 
         /// The flush as a pair (pisces_hip_flush_begin / pisces_hip_flush_end_view): FlushBegin enqueues the device work of the batch and
@@ -207,7 +224,7 @@ namespace Pisces.Hip
         {
             PiscesCalledAllele* rows; int* idx; PiscesCandidate* cands; byte* pool; long n, nc, nb;
             NativeMethods.Check(_h, NativeMethods.pisces_hip_flush_end_view(_h, out rows, out n, out idx, out cands, out nc, out pool, out nb));
-            return ToCalledAlleles(chr, rows, n, idx, cands, pool);
+            return ToCalledAlleles(chr, rows, n, idx, cands, pool, PosteriorsOfLastFlush(n));
         }
 
         private bool HeldBack(int? upToPosition)
@@ -219,8 +236,19 @@ namespace Pisces.Hip
             return false;
         }
 
-        /// rows (valid until the next flush on the handle) -> CalledAllele objects; idx == null: no row has a candidate (Reference / SNV rows only)
-        private static unsafe SortedList<int, List<CalledAllele>> ToCalledAlleles(ChrReference chr, PiscesCalledAllele* recs, long n, int* idx, PiscesCandidate* cands, byte* pool)
+        /// the posteriors of the rows a flush view has just handed out (row-parallel, valid as long as the rows are); null for the other ploidy models
+        private unsafe PiscesGenotypePosteriors* PosteriorsOfLastFlush(long nRows)
+        {
+            if (_cfg.Ploidy != 3) return null;
+            PiscesGenotypePosteriors* gp; long n;
+            NativeMethods.Check(_h, NativeMethods.pisces_hip_posteriors_view(_h, out gp, out n));
+            return n == nRows ? gp : null;
+        }
+
+        /// rows (valid until the next flush on the handle) -> CalledAllele objects; idx == null: no row has a candidate (Reference / SNV rows only);
+        /// gp != null: CalledAllele.GenotypePosteriors of every row that has them
+        private static unsafe SortedList<int, List<CalledAllele>> ToCalledAlleles(ChrReference chr, PiscesCalledAllele* recs, long n, int* idx, PiscesCandidate* cands, byte* pool,
+                                                                                  PiscesGenotypePosteriors* gp)
         {
             var result = new SortedList<int, List<CalledAllele>>();
             const string baseOf = "AGCTND";
@@ -252,6 +280,12 @@ namespace Pisces.Hip
                 a.StrandBiasResults.VarPresentOnBothStrands = ((r.Info >> 14) & 1) != 0;
                 a.StrandBiasResults.CovPresentOnBothStrands = ((r.Info >> 15) & 1) != 0;
                 foreach (var f in FilterOrder) if ((r.FilterBits & (1 << (int)f.Item1)) != 0) a.AddFilter(f.Item2);
+                if (gp != null && gp[i].N > 0)
+                {
+                    var posteriors = new float[gp[i].N];
+                    for (int k = 0; k < posteriors.Length; k++) posteriors[k] = gp[i].Gp[k];
+                    a.GenotypePosteriors = posteriors;
+                }
                 List<CalledAllele> at;
                 if (!result.TryGetValue(r.Position, out at)) { at = new List<CalledAllele>(); result.Add(r.Position, at); }
                 at.Add(a);                                              // rows arrive sorted by position, then (ref, alt)

@@ -63,6 +63,7 @@ namespace Pisces.Hip
             // own HIP stream and buffers; handles share nothing).  PISCES_HIP_DEVICE pins one device (a process per GPU, as bench.py runs).
             _engine = new HipEngine(HipEngine.ConfigFrom(_options, expectStitchedReads, intervalSet != null), NextDevice());
             if (intervalSet != null) _engine.SetIntervals(intervalSet);
+            _engine.SetAdaptiveGenotypingParameters(_options.VariantCallingParameters.AdaptiveGenotypingParameters);   // (DiploidByAdaptiveGT only)
             _engine.SetForcedAlleles(_forcedGtAlleles);   // -forcedalleles: ForcedReport rows, reference rows at forced positions
             return new HipStateManager(_engine);
         }

@@ -57,6 +57,24 @@ namespace Pisces.Hip
     }
 
     [StructLayout(LayoutKind.Sequential)]
+    public unsafe struct PiscesAdaptiveParams   // AdaptiveGenotypingParameters (Pisces.Domain/Options/VariantCallingParameters.cs:28-55)
+    {
+        public fixed double SnvModel[3];
+        public fixed double IndelModel[3];
+        public fixed double SnvPrior[3];
+        public fixed double IndelPrior[3];
+        public float SumVfForMultiAllelicSite;
+        public int MaxGenotypePosteriors;
+    }
+
+    [StructLayout(LayoutKind.Sequential, Size = 32)]
+    public unsafe struct PiscesGenotypePosteriors   // CalledAllele.GenotypePosteriors of one row: N = 3, 6 (a 1/2 locus) or 0 (null)
+    {
+        public fixed float Gp[6];
+        public int N, Reserved;
+    }
+
+    [StructLayout(LayoutKind.Sequential)]
     public struct PiscesGenotypeAllele   // one allele of a locus for pisces_hip_set_genotypes (the germline genotypers as a function)
     {
         public int Category, RefLen, AltLen, Support, Coverage, ReferenceSupport;
@@ -200,6 +218,17 @@ namespace Pisces.Hip
         /// the host half of IAlleleCaller.Call as functions: MnvReallocator.ReallocateFailedMnvs and the germline genotypers on alleles the caller brings
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pisces_hip_reallocate_failed_mnvs(PiscesCandidate[] failed, long nFailed, PiscesCandidate[] callable, long nCallable, byte[] alleles, long alleleBytes, int blockMaxPosition, [Out] PiscesCandidate[] callableOut, long callableCapacity, out long nCallableOut, [Out] PiscesCandidate[] outsideOut, long outsideCapacity, out long nOutsideOut, [Out] byte[] allelesOut, long alleleCapacity, out long alleleBytesOut);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pisces_hip_set_genotypes(ref PiscesHipConfig cfg, [In, Out] PiscesGenotypeAllele[] allelesOfOneLocus, int n, byte[] alleles, long alleleBytes);
+        // PloidyModel.DiploidByAdaptiveGT: the mixture's parameters, the rows' posteriors (row i of the last flush <-> entry i), the host-only genotyper
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pisces_hip_adaptive_default_params(out PiscesAdaptiveParams p);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pisces_hip_set_adaptive_params(IntPtr handle, ref PiscesAdaptiveParams p);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pisces_hip_get_posteriors(IntPtr handle, [Out] PiscesGenotypePosteriors[] rows, long capacity, out long n);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pisces_hip_posteriors_view(IntPtr handle, out PiscesGenotypePosteriors* rows, out long n);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pisces_hip_set_posteriors_buffer(IntPtr handle, IntPtr dPosteriors, long capacity);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pisces_hip_compact_posteriors(IntPtr handle, IntPtr dPosteriors, IntPtr dTileResults, int nTiles, IntPtr dOffsets, IntPtr dOut, int outCapacity, IntPtr stream);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pisces_hip_set_genotypes_adaptive(ref PiscesHipConfig cfg, ref PiscesAdaptiveParams p, [In, Out] PiscesGenotypeAllele[] allelesOfOneLocus, int n, byte[] alleles, long alleleBytes, [Out] PiscesGenotypePosteriors[] posteriors);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pisces_hip_adaptive_genotype_qscore(ref PiscesAdaptiveParams p, int category, int isReference, int alleleSupport, int totalCoverage, out int categoryOut, out int qscoreOut, [Out] float[] gp3);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern long pisces_hip_format_vcf_ex(ref PiscesVcfConfig cfg, [MarshalAs(UnmanagedType.LPStr)] string chrom, PiscesCalledAllele[] records, long n, int[] candIndex, PiscesCandidate[] cands, byte[] alleles, [Out] byte[] text, long capacity, PiscesGenotypePosteriors[] gp);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern long pisces_hip_format_vcf_padded_ex(ref PiscesVcfConfig cfg, [MarshalAs(UnmanagedType.LPStr)] string chrom, PiscesCalledAllele[] records, long n, int[] candIndex, PiscesCandidate[] cands, byte[] alleles, byte[] referenceBases, long refLen, int[] intervalStarts, int[] intervalEnds, int nIntervals, ref PiscesVcfPadState state, int finish, [Out] byte[] text, long capacity, PiscesGenotypePosteriors[] gp);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pisces_hip_diploid_genotype_qscore(int genotype, int totalCoverage, int alleleSupport, int minQscore, int maxQscore);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pisces_hip_vcf_default_config(out PiscesVcfConfig cfg);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern long pisces_hip_format_vcf(ref PiscesVcfConfig cfg, [MarshalAs(UnmanagedType.LPStr)] string chrom, PiscesCalledAllele[] records, long n, int[] candIndex, PiscesCandidate[] cands, byte[] alleles, [Out] byte[] text, long capacity);

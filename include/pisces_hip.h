@@ -58,8 +58,9 @@ enum { PISCES_FILTER_STRAND_BIAS = 0, PISCES_FILTER_POOL_BIAS = 1, PISCES_FILTER
 /* src/lib/Pisces.Domain/Types (StrandBiasModel): Poisson, Extended, Diploid */
 enum { PISCES_SB_POISSON = 0, PISCES_SB_EXTENDED = 1, PISCES_SB_DIPLOID = 2 };
 enum { PISCES_NOISE_FLAT = 0, PISCES_NOISE_WINDOW = 1 };
-enum { PISCES_PLOIDY_SOMATIC = 0, PISCES_PLOIDY_DIPLOID = 1, PISCES_PLOIDY_HAPLOID = 2 };   /* PloidyModel.Somatic / DiploidByThresholding /
-                                                                                         Haploid (Types/ModelTypes.cs) */   /* Pisces.Domain/Types/ModelTypes.cs:13 */
+enum { PISCES_PLOIDY_SOMATIC = 0, PISCES_PLOIDY_DIPLOID = 1, PISCES_PLOIDY_HAPLOID = 2,
+       PISCES_PLOIDY_DIPLOID_ADAPTIVE = 3 };   /* PloidyModel.Somatic / DiploidByThresholding / Haploid / DiploidByAdaptiveGT
+                                                  (Pisces.Domain/Types/ModelTypes.cs:13) */
 
 /* Anchor bins: NumAnchorIndexes = 2*trackedAnchorSize+1 (RegionStateManager.cs:30-31), default 5 -> 11 */
 #define PISCES_ANCHOR_SIZE   5
@@ -147,7 +148,8 @@ typedef struct PiscesHipConfig {
     int32_t noise_model;              /* VariantCallingParameters.NoiseModel: PISCES_NOISE_FLAT (default) or PISCES_NOISE_WINDOW, where the
                                          variant q-score of an allele uses (int)PtoQ(SumOfBaseQuality / TotalCoverage) as its noise level
                                          (AlleleCaller.cs:215-218, RegionStateManager.cs:191) */
-    int32_t ploidy;                   /* PISCES_PLOIDY_SOMATIC (default), PISCES_PLOIDY_DIPLOID or PISCES_PLOIDY_HAPLOID: one genotype per locus from the
+    int32_t ploidy;                   /* PISCES_PLOIDY_SOMATIC (default), PISCES_PLOIDY_DIPLOID, PISCES_PLOIDY_HAPLOID or
+                                         PISCES_PLOIDY_DIPLOID_ADAPTIVE (the mixture model, see PiscesAdaptiveParams): one genotype per locus from the
                                          variant frequencies, alleles beyond the ploidy pruned (DiploidThresholdingGenotyper.cs:54-141,
                                          HaploidGenotyper.cs:36-83, which takes MinorVF / MajorVF from the SNV parameters below).  Made on the
                                          device over the tile kernels' record slots (pisces_hip_call_tiles*, and a flush whose rows are
@@ -194,6 +196,31 @@ typedef struct PiscesCalledAllele {
 #define PISCES_INFO_PACK(gt, cat, ref, alt, sbok, varboth, covboth) \
     ((uint16_t)((gt) | ((cat) << 4) | ((ref) << 7) | ((alt) << 10) | ((sbok) << 13) | \
                 ((varboth) << 14) | ((covboth) << 15)))
+
+/* ---- PloidyModel.DiploidByAdaptiveGT (src/lib/Pisces.Genotyping/Adaptive/DiploidAdaptiveGenotyper.cs:45-176, AdaptiveGenotyperCalculator.cs:18-82,
+ * MixtureModel.cs:281-346, 378-406, 449-518): the genotype of a locus is the most probable component of a three-component binomial mixture
+ * (hom-ref, het, hom-alt) at the dominant variant's depth, the genotype q-score and the phred-scaled genotype posteriors (the VCF GP column)
+ * come from the same mixture at effective depths {25, 25, 10}; a 1/2 locus gets six posteriors from a multinomial.  The means and priors are
+ * AdaptiveGenotypingParameters (src/lib/Pisces.Domain/Options/VariantCallingParameters.cs:28-55); fitting them (the stand-alone
+ * recalibration tool's EM) is not part of the library.  In this mode the reference leaves VariantCallerConfig.MinFrequency at 0
+ * (exe/Pisces/Logic/Factory.cs:128-147: the adaptive genotyper never sets MinVarFrequency) and uses SomaticLocusProcessor: a host sets
+ * cfg.min_frequency = 0 itself, and forced alleles get no DiploidLocusProcessor treatment. */
+typedef struct PiscesAdaptiveParams {
+    double  snv_model[3];                   /* SnvModel {0.037, 0.439, 0.976}: SNV, MNV and Reference alleles */
+    double  indel_model[3];                 /* IndelModel {0.037, 0.443, 0.905}: insertions and deletions */
+    double  snv_prior[3];                   /* SnvPrior {0.755, 0.154, 0.0919} */
+    double  indel_prior[3];                 /* IndelPrior {0.962, 0.0266, 0.0114} */
+    float   sum_vf_for_multi_allelic_site;  /* SumVFforMultiAllelicSite, 0.80f */
+    int32_t max_genotype_posteriors;        /* MaxGenotypePosteriors, 3000: the three posteriors of an allele without coverage */
+} PiscesAdaptiveParams;
+/* CalledAllele.GenotypePosteriors of one row (32 bytes): n = 3 {hom-ref, het, hom-alt}, 6 at a 1/2 locus (MixtureModel.cs:449-518), 0 = null
+ * (a row no adaptive genotyper touched: every row of another ploidy, a forced-report row).  A row and its posteriors share one index
+ * wherever rows leave the library. */
+typedef struct PiscesGenotypePosteriors {
+    float   gp[6];
+    int32_t n;
+    int32_t reserved;
+} PiscesGenotypePosteriors;
 
 /* ---- tile descriptor: a run of <= tile_loci consecutive reference positions ------------
  * The unit of device work and of interval sharding.  Tiles of one call must
@@ -361,6 +388,18 @@ int32_t pisces_hip_flush_view(PiscesHip* h, int32_t up_to_position, const Pisces
                               const PiscesCandidate** cands, int64_t* n_cand, const uint8_t** alleles, int64_t* allele_bytes);
 int32_t pisces_hip_flush_end_view(PiscesHip* h, const PiscesCalledAllele** rows, int64_t* n_rows, const int32_t** cand_index,
                                   const PiscesCandidate** cands, int64_t* n_cand, const uint8_t** alleles, int64_t* allele_bytes);
+/* PloidyModel.DiploidByAdaptiveGT: the mixture's parameters.  A handle created with PISCES_PLOIDY_DIPLOID_ADAPTIVE starts with
+ * pisces_hip_adaptive_default_params (the reference's defaults).  PISCES_E_INVALID_ARG for means or priors outside (0, 1) or means that do
+ * not ascend, PISCES_E_STATE on a handle of another ploidy.  Any time before the flush / launch that should see them. */
+int32_t pisces_hip_adaptive_default_params(PiscesAdaptiveParams* params);
+int32_t pisces_hip_set_adaptive_params(PiscesHip* h, const PiscesAdaptiveParams* params);
+/* CalledAllele.GenotypePosteriors of the rows the most recent pisces_hip_flush / _flush_ex / _flush_view / _flush_end* handed out: same
+ * order, same count (*n_out; PISCES_E_BUFFER_TOO_SMALL with *n_out = the count needed when capacity is short, nothing is lost).  Rows of
+ * a handle of another ploidy, and forced-report rows, have n = 0.  pisces_hip_posteriors_view: where they lie in memory of the handle, valid
+ * as long as the rows of pisces_hip_flush_view / pisces_hip_flush_end_view are (until the next flush on the handle; same thread as the
+ * flush).  In a flush the adaptive genotyper is the host pass over the merged rows. */
+int32_t pisces_hip_get_posteriors(PiscesHip* h, PiscesGenotypePosteriors* out, int64_t capacity, int64_t* n_out);
+int32_t pisces_hip_posteriors_view(PiscesHip* h, const PiscesGenotypePosteriors** rows, int64_t* n_rows);
 /* IAlleleSource.GetAlleleCount for a run of positions: out[n][6][3][11] int32
  * (RegionState.cs:57); blocks never touched read as zero (RegionStateManager.cs:222-226). */
 int32_t pisces_hip_get_counts(PiscesHip* h, int32_t start_position, int32_t n, int32_t* out);
@@ -505,6 +544,17 @@ int32_t pisces_hip_call_tiles_graph_launch(PiscesHip* h, int32_t graph_id, void*
 int32_t pisces_hip_compact_records(PiscesHip* h, const PiscesCalledAllele* d_records,
                                    const PiscesTileResult* d_tile_results, int32_t n_tiles, int32_t* d_offsets,
                                    PiscesCalledAllele* d_out, int32_t out_capacity, int32_t* d_count, void* stream);
+/* PloidyModel.DiploidByAdaptiveGT on the device-resident surface: names the device buffer, slot-parallel to d_records (entry i = the
+ * posteriors of record slot i; capacity >= 256 * n_tiles entries, else pisces_hip_call_tiles returns PISCES_E_BUFFER_TOO_SMALL), that every
+ * later pisces_hip_call_tiles of this handle fills behind its tile kernel; capacity 0 = none (genotypes and q-scores only).
+ * PISCES_E_STATE on a handle of another ploidy.  pisces_hip_call_tiles_batched and pisces_hip_call_tiles_graph_build refuse an adaptive
+ * handle with PISCES_E_UNSUPPORTED (one posteriors buffer a handle). */
+int32_t pisces_hip_set_posteriors_buffer(PiscesHip* h, PiscesGenotypePosteriors* d_posteriors, int64_t capacity);
+/* The posteriors in the order of pisces_hip_compact_records' output: d_out[i] belongs to its d_out[i].  d_offsets is what
+ * pisces_hip_compact_records left there for the same d_tile_results (call it first, on the same stream).  Asynchronous. */
+int32_t pisces_hip_compact_posteriors(PiscesHip* h, const PiscesGenotypePosteriors* d_posteriors, const PiscesTileResult* d_tile_results,
+                                      int32_t n_tiles, const int32_t* d_offsets, PiscesGenotypePosteriors* d_out, int32_t out_capacity,
+                                      void* stream);
 /* tuples -> anchor-resolved counts added into d_counts[n_tiles*tile_loci][6][3][11]
  * (the IAlleleSource view for host-side collapsing / spanning coverage). Asynchronous. */
 int32_t pisces_hip_accumulate_tiles(PiscesHip* h, const uint32_t* d_tuples, const PiscesTile* d_tiles,
@@ -606,6 +656,16 @@ typedef struct PiscesGenotypeAllele {
 } PiscesGenotypeAllele;
 int32_t pisces_hip_set_genotypes(const PiscesHipConfig* cfg, PiscesGenotypeAllele* alleles_of_one_locus, int32_t n, const uint8_t* alleles,
                                  int64_t allele_bytes);
+/* DiploidAdaptiveGenotyper.SetGenotypes (Adaptive/DiploidAdaptiveGenotyper.cs:45-176) over the alleles of ONE locus, n >= 1, in the caller's
+ * order (the 1/2 multinomial takes the first two as given, a Reference row included): minimum depth and q-score range from cfg, the mixture
+ * from params; posteriors_out[n] (may be NULL) receives every allele's posteriors, the pruned ones' too.  Returns the locus' genotype or < 0. */
+int32_t pisces_hip_set_genotypes_adaptive(const PiscesHipConfig* cfg, const PiscesAdaptiveParams* params, PiscesGenotypeAllele* alleles_of_one_locus,
+                                          int32_t n, const uint8_t* alleles, int64_t allele_bytes, PiscesGenotypePosteriors* posteriors_out);
+/* AdaptiveGenotyperCalculator.GetGenotypeAndQScore (AdaptiveGenotyperCalculator.cs:32-36) for one allele with coverage: the mixture component
+ * (0 hom-ref, 1 het, 2 hom-alt), the q-score before the handle's [min, max] clamp (0..100) and three phred-scaled posteriors; `category`
+ * (PISCES_CAT_*) selects the SNV or the indel pair, is_reference the reference allele's depth (coverage - support). */
+int32_t pisces_hip_adaptive_genotype_qscore(const PiscesAdaptiveParams* params, int32_t category, int32_t is_reference, int32_t allele_support,
+                                            int32_t total_coverage, int32_t* category_out, int32_t* qscore_out, float* gp_out);
 /* DiploidGenotypeQualityCalculator.Compute (Thresholding/DiploidGenotypeQualityCalculator.cs:17-103) for one allele */
 int32_t pisces_hip_diploid_genotype_qscore(int32_t genotype, int32_t total_coverage, int32_t allele_support, int32_t min_qscore, int32_t max_qscore);
 
@@ -647,6 +707,17 @@ int64_t pisces_hip_format_vcf_padded(const PiscesVcfConfig* cfg, const char* chr
                                      const uint8_t* ref_bases, int64_t ref_len, const int32_t* interval_starts,
                                      const int32_t* interval_ends, int32_t n_intervals, PiscesVcfPadState* state, int32_t finish,
                                      char* out, int64_t capacity);
+/* The two entries above with CalledAllele.GenotypePosteriors: gp[i] belongs to recs[i] (NULL: exactly the bytes of the entries above).
+ * A line whose first allele has gp.n > 0 gets ":GP" behind its FORMAT keys and the values, each "0.00", comma-joined, behind its sample
+ * (VcfFormatter.cs:263-269; ShouldReportGp is on with DiploidByAdaptiveGT); RegionMapper's no-call rows have none. */
+int64_t pisces_hip_format_vcf_ex(const PiscesVcfConfig* cfg, const char* chrom, const PiscesCalledAllele* recs, int64_t n,
+                                 const int32_t* cand_index, const PiscesCandidate* cands, const uint8_t* alleles, char* out,
+                                 int64_t capacity, const PiscesGenotypePosteriors* gp);
+int64_t pisces_hip_format_vcf_padded_ex(const PiscesVcfConfig* cfg, const char* chrom, const PiscesCalledAllele* recs, int64_t n,
+                                        const int32_t* cand_index, const PiscesCandidate* cands, const uint8_t* alleles,
+                                        const uint8_t* ref_bases, int64_t ref_len, const int32_t* interval_starts,
+                                        const int32_t* interval_ends, int32_t n_intervals, PiscesVcfPadState* state, int32_t finish,
+                                        char* out, int64_t capacity, const PiscesGenotypePosteriors* gp);
 
 /* ---- BGZF inflate on the device (the stage upstream of the read batch) ------------------------------------
  * A BAM file is a chain of BGZF blocks, gzip members of <= 64 KiB whose 'BC' extra subfield holds the block size; each is an

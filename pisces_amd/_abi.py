@@ -36,6 +36,8 @@ GT_STRING = {GT_HET_ALT_REF: "0/1", GT_HOM_ALT: "1/1", GT_HOM_REF: "0/0", GT_REF
  FILTER_LOW_VARIANT_FREQUENCY, FILTER_LOW_GENOTYPE_QUALITY, FILTER_INDEL_REPEAT_LENGTH,
  FILTER_MULTI_ALLELIC_SITE, FILTER_RMXN, FILTER_FORCED_REPORT, FILTER_OFF_TARGET, FILTER_NO_CALL) = range(13)
 SB_POISSON, SB_EXTENDED, SB_DIPLOID = range(3)
+# src/lib/Pisces.Domain/Types/ModelTypes.cs: PloidyModel.Somatic / DiploidByThresholding / Haploid / DiploidByAdaptiveGT
+PLOIDY_SOMATIC, PLOIDY_DIPLOID, PLOIDY_HAPLOID, PLOIDY_DIPLOID_ADAPTIVE = range(4)
 
 ANCHOR_SIZE = 5
 NUM_ANCHORS = 11
@@ -273,6 +275,21 @@ class PiscesGenotypeAllele(C.Structure):
         ("genotype", C.c_int32), ("genotype_qscore", C.c_int32), ("phase_set_index", C.c_int32),
         ("multi_allelic", C.c_uint8), ("prune", C.c_uint8), ("pad", C.c_uint8 * 2),
     ]
+
+
+class PiscesAdaptiveParams(C.Structure):
+    """AdaptiveGenotypingParameters (VariantCallingParameters.cs:28-55), see include/pisces_hip.h"""
+    _fields_ = [("snv_model", C.c_double * 3), ("indel_model", C.c_double * 3), ("snv_prior", C.c_double * 3), ("indel_prior", C.c_double * 3),
+                ("sum_vf_for_multi_allelic_site", C.c_float), ("max_genotype_posteriors", C.c_int32)]
+
+
+class PiscesGenotypePosteriors(C.Structure):
+    _fields_ = [("gp", C.c_float * 6), ("n", C.c_int32), ("reserved", C.c_int32)]
+
+
+# one PiscesGenotypePosteriors per row (CalledAllele.GenotypePosteriors): n = 3, 6 (a 1/2 locus) or 0 (none)
+POSTERIORS_DTYPE = np.dtype([("gp", "<f4", (6,)), ("n", "<i4"), ("reserved", "<i4")], align=False)
+assert POSTERIORS_DTYPE.itemsize == 32
 
 
 class PiscesBgzfBlock(C.Structure):

@@ -23,6 +23,8 @@ EXPORTS = [
     "pisces_hip_add_candidates", "pisces_hip_set_forced_alleles", "pisces_hip_host_time", "pisces_hip_set_owned_range", "pisces_hip_bam_fetch_directions", "pisces_hip_call_tiles_graph_build", "pisces_hip_call_tiles_graph_launch", "pisces_hip_mark", "pisces_hip_marked_ms",
     "pisces_hip_flush_end_ex", "pisces_hip_device_count", "pisces_hip_flush_view", "pisces_hip_flush_end_view", "pisces_hip_transfer_bytes",
     "pisces_hip_add_device_reads", "pisces_hip_get_stream", "pisces_hip_comm_library", "pisces_hip_comm_ranks", "pisces_hip_set_known_variants", "pisces_hip_set_exclude_mnvs_from_collapsing", "pisces_hip_set_exact_total_called", "pisces_hip_reallocate_failed_mnvs", "pisces_hip_set_genotypes", "pisces_hip_diploid_genotype_qscore",
+    "pisces_hip_adaptive_default_params", "pisces_hip_set_adaptive_params", "pisces_hip_get_posteriors", "pisces_hip_posteriors_view", "pisces_hip_set_posteriors_buffer",
+    "pisces_hip_compact_posteriors", "pisces_hip_set_genotypes_adaptive", "pisces_hip_adaptive_genotype_qscore", "pisces_hip_format_vcf_ex", "pisces_hip_format_vcf_padded_ex",
 ]
 
 
@@ -70,6 +72,14 @@ def _load():
         "pisces_hip_reallocate_failed_mnvs": (i32, [vp, i64, vp, i64, vp, i64, i32, vp, i64, P(i64), vp, i64, P(i64), vp, i64, P(i64)]),
         "pisces_hip_set_genotypes": (i32, [P(_abi.PiscesHipConfig), P(_abi.PiscesGenotypeAllele), i32, vp, i64]),
         "pisces_hip_diploid_genotype_qscore": (i32, [i32, i32, i32, i32, i32]),
+        "pisces_hip_adaptive_default_params": (i32, [P(_abi.PiscesAdaptiveParams)]),
+        "pisces_hip_set_adaptive_params": (i32, [vp, P(_abi.PiscesAdaptiveParams)]),
+        "pisces_hip_get_posteriors": (i32, [vp, vp, i64, P(i64)]),
+        "pisces_hip_posteriors_view": (i32, [vp, P(vp), P(i64)]),
+        "pisces_hip_set_posteriors_buffer": (i32, [vp, vp, i64]),
+        "pisces_hip_compact_posteriors": (i32, [vp, vp, vp, i32, vp, vp, i32, vp]),
+        "pisces_hip_set_genotypes_adaptive": (i32, [P(_abi.PiscesHipConfig), P(_abi.PiscesAdaptiveParams), P(_abi.PiscesGenotypeAllele), i32, vp, i64, vp]),
+        "pisces_hip_adaptive_genotype_qscore": (i32, [P(_abi.PiscesAdaptiveParams), i32, i32, i32, i32, P(i32), P(i32), P(C.c_float)]),
         "pisces_hip_stage_reads": (i32, [vp, i32, i64, i64, i32, i32, P(_abi.PiscesReadBatch)]),
         "pisces_hip_flush_begin": (i32, [vp, i32]),
         "pisces_hip_flush_end": (i32, [vp, vp, i64, P(i64)]),
@@ -133,6 +143,9 @@ def _load():
         "pisces_hip_format_vcf": (i64, [P(_abi.PiscesVcfConfig), C.c_char_p, vp, i64, vp, vp, vp, vp, i64]),
         "pisces_hip_format_vcf_padded": (i64, [P(_abi.PiscesVcfConfig), C.c_char_p, vp, i64, vp, vp, vp, vp, i64, vp, vp, i32,
                                                P(_abi.PiscesVcfPadState), i32, vp, i64]),
+        "pisces_hip_format_vcf_ex": (i64, [P(_abi.PiscesVcfConfig), C.c_char_p, vp, i64, vp, vp, vp, vp, i64, vp]),
+        "pisces_hip_format_vcf_padded_ex": (i64, [P(_abi.PiscesVcfConfig), C.c_char_p, vp, i64, vp, vp, vp, vp, i64, vp, vp, i32,
+                                                  P(_abi.PiscesVcfPadState), i32, vp, i64, vp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(lib, name)   # AttributeError here = a declared symbol is not exported

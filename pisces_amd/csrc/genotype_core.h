@@ -1,10 +1,10 @@
-// genotype_core.h — PloidyModel.DiploidByThresholding / Haploid for the alleles of ONE locus, one source for the host and the device
-// (src/lib/Pisces.Genotyping/Thresholding/DiploidThresholdingGenotyper.cs:54-141, GenotypeCalculatorUtilities.cs:11-237,
+// genotype_core.h — PloidyModel.DiploidByThresholding / Haploid / DiploidByAdaptiveGT for the alleles of ONE locus, one source for the host and the device
+// (src/lib/Pisces.Genotyping/Thresholding/DiploidThresholdingGenotyper.cs:54-141, GenotypeCalculatorUtilities.cs:11-237, Adaptive/*.cs,
 // DiploidGenotypeQualityCalculator.cs:12-105, Haploid/HaploidGenotyper.cs:36-83, HaploidGenotypeQualityCalculator.cs:10-59; the ln PMFs are
 // MathNet.Numerics 4.5.1's Poisson.ProbabilityLn / Binomial.ProbabilityLn with its GammaLn / FactorialLn).
 //   diploid.cpp                 the host form: the per-locus pass of a flush whose rows come from two kernels, pisces_hip_set_genotypes
-//   genotype_loci_kernel        (kernels.hip.h) lane = locus over the tile kernels' record slots: the device-resident surface and the
-//                               flushes that have no candidate rows
+//   genotype_loci_kernel,       (kernels.hip.h) lane = locus over the tile kernels' record slots: the device-resident surface and the
+//   genotype_loci_adaptive_kernel flushes that have no candidate rows
 // The alleles are plain records; the order of two alleles of equal frequency (ordinal order of their REF, then ALT strings) comes from the
 // caller: strings on the host, the slot rank (A C G T) on the device.
 #pragma once
@@ -149,6 +149,41 @@ PISCES_GHD inline double reference_frequency(const Allele* a, int n)
     return refBySNP - indelCount > 0.0 ? refBySNP - indelCount : 0.0;
 }
 
+// ConvertSimpleGenotypeToComplexGenotype with CheckForTriAllelicIssue and SetMultiAllelicFilter (GenotypeCalculatorUtilities.cs:135-234);
+// prelim: 0 HomozygousRef, 1 HeterozygousAltRef, 2 HomozygousAlt; order[0..nv) = the variants by descending frequency
+PISCES_GHD inline int32_t complex_genotype(Allele* a, int n, const int* order, int nv, double referenceFrequency, bool refExists, bool depthIssue, bool refCall,
+                                           float minVarFrequency, float sumVFforMultiAllelicSite, int prelim)
+{
+    if (depthIssue) return refCall ? PISCES_GT_REF_LIKE_NOCALL : PISCES_GT_ALT_LIKE_NOCALL;
+    if (prelim == 0) {
+        if (!refExists) return PISCES_GT_REF_LIKE_NOCALL;
+        return (n > 0 && a[0].category == PISCES_CAT_REFERENCE && (1 - frequency_of(a[0].support, a[0].coverage)) > minVarFrequency) ? PISCES_GT_REF_AND_NOCALL
+                                                                                                                                   : PISCES_GT_HOM_REF;
+    }
+    if (prelim == 1) {
+        if (nv == 1) return refExists ? PISCES_GT_HET_ALT_REF : PISCES_GT_ALT_AND_NOCALL;
+        const float f0 = frequency_of(a[order[0]].support, a[order[0]].coverage);
+        bool fail;   // CheckForTriAllelicIssue
+        if (a[order[nv - 1]].category != PISCES_CAT_SNV) fail = false;
+        else if (refExists && ((double)f0 + referenceFrequency) < (double)sumVFforMultiAllelicSite) fail = true;
+        else fail = (f0 + frequency_of(a[order[1]].support, a[order[1]].coverage)) < sumVFforMultiAllelicSite;
+        if (fail) {
+            for (int i = 0; i < n; i++) a[i].multi_allelic = true;
+            return refExists ? PISCES_GT_ALT_LIKE_NOCALL : PISCES_GT_ALT12_LIKE_NOCALL;
+        }
+        return refExists ? PISCES_GT_HET_ALT_REF : PISCES_GT_HET_ALT1_ALT2;
+    }
+    return PISCES_GT_HOM_ALT;
+}
+// GetAllelesToPruneBasedOnGTCall (GenotypeCalculatorUtilities.cs:11-47)
+PISCES_GHD inline void prune_beyond_genotype(Allele* a, const int* order, int nv, int32_t gt)
+{
+    int allowed = 0;
+    if (gt == PISCES_GT_ALT_AND_NOCALL || gt == PISCES_GT_ALT_LIKE_NOCALL || gt == PISCES_GT_HOM_ALT || gt == PISCES_GT_HET_ALT_REF) allowed = 1;
+    else if (gt == PISCES_GT_ALT12_LIKE_NOCALL || gt == PISCES_GT_HET_ALT1_ALT2) allowed = 2;
+    for (int k = allowed; k < nv; k++) a[order[k]].prune = true;
+}
+
 // DiploidThresholdingGenotyper.SetGenotypes over the alleles of one locus (Reference rows already gone when a variant is there);
 // snv / indel = {MinorVF, MajorVF, SumVFforMultiAllelicSite}.  Returns the locus genotype.
 template <typename Before>
@@ -165,32 +200,8 @@ PISCES_GHD inline int32_t diploid_set(Allele* a, int n, int* order, const float 
     const float* par = (!refCall && a[order[0]].category != PISCES_CAT_SNV) ? indel : snv;   // SelectParameters
     int prelim = 0;   // GetPreliminaryGenotype: 0 HomozygousRef, 1 HeterozygousAltRef, 2 HomozygousAlt
     if (!refCall) prelim = (f0 >= par[0] && f0 <= par[1]) ? 1 : (f0 > par[1]) ? 2 : 0;
-    // ConvertSimpleGenotypeToComplexGenotype
-    int32_t gt;
-    if (depthIssue) gt = refCall ? PISCES_GT_REF_LIKE_NOCALL : PISCES_GT_ALT_LIKE_NOCALL;
-    else if (prelim == 0) {
-        if (!refExists) gt = PISCES_GT_REF_LIKE_NOCALL;
-        else gt = (n > 0 && a[0].category == PISCES_CAT_REFERENCE && (1 - frequency_of(a[0].support, a[0].coverage)) > par[0]) ? PISCES_GT_REF_AND_NOCALL : PISCES_GT_HOM_REF;
-    } else if (prelim == 1) {
-        if (nv == 1) gt = refExists ? PISCES_GT_HET_ALT_REF : PISCES_GT_ALT_AND_NOCALL;
-        else {
-            bool fail;   // CheckForTriAllelicIssue
-            if (a[order[nv - 1]].category != PISCES_CAT_SNV) fail = false;
-            else if (refExists && ((double)f0 + referenceFrequency) < (double)par[2]) fail = true;
-            else fail = (f0 + frequency_of(a[order[1]].support, a[order[1]].coverage)) < par[2];
-            if (fail) {
-                for (int i = 0; i < n; i++) a[i].multi_allelic = true;
-                gt = refExists ? PISCES_GT_ALT_LIKE_NOCALL : PISCES_GT_ALT12_LIKE_NOCALL;
-            } else {
-                gt = refExists ? PISCES_GT_HET_ALT_REF : PISCES_GT_HET_ALT1_ALT2;
-            }
-        }
-    } else gt = PISCES_GT_HOM_ALT;
-    // GetAllelesToPruneBasedOnGTCall
-    int allowed = 0;
-    if (gt == PISCES_GT_ALT_AND_NOCALL || gt == PISCES_GT_ALT_LIKE_NOCALL || gt == PISCES_GT_HOM_ALT || gt == PISCES_GT_HET_ALT_REF) allowed = 1;
-    else if (gt == PISCES_GT_ALT12_LIKE_NOCALL || gt == PISCES_GT_HET_ALT1_ALT2) allowed = 2;
-    for (int k = allowed; k < nv; k++) a[order[k]].prune = true;
+    const int32_t gt = complex_genotype(a, n, order, nv, referenceFrequency, refExists, depthIssue, refCall, par[0], par[2], prelim);
+    prune_beyond_genotype(a, order, nv, gt);
     // SetGenotypes
     int phase = 1;
     for (int i = 0; i < n; i++) {
@@ -232,6 +243,221 @@ PISCES_GHD inline int32_t haploid_set(Allele* a, int n, int* order, float minorV
             gq = clamp_q(floor(10.0 * 0.4342944819032518 * (h0 - h1)), minGQ, maxGQ);
         }
         a[i].genotype_qscore = gq;
+    }
+    return gt;
+}
+
+// ---- PloidyModel.DiploidByAdaptiveGT (Adaptive/DiploidAdaptiveGenotyper.cs:45-176, AdaptiveGenotyperCalculator.cs:18-82, MixtureModel.cs:281-346,
+// 378-406, 449-518; MathNet.Numerics 4.5.1's Binomial.PMF, Normal.PDF and Multinomial.Probability restated) -----------------------------------
+PISCES_GHD inline double binomial_pmf(double p, int n, int k) { return exp(binomial_ln_pmf(p, n, k)); }   // Binomial.PMF
+PISCES_GHD inline double normal_pdf(double mean, double sd, double x)                                      // Normal.PDF
+{
+    const double d = (x - mean) / sd;
+    return exp(-0.5 * d * d) / (2.5066282746310005024 * sd);
+}
+// Multinomial(p, n).Probability(x) over three classes: the rounded coefficient times the product of powers; p as given (not normalised)
+PISCES_GHD inline double multinomial_probability(const double p[3], int n, const int x[3])
+{
+    if (x[0] + x[1] + x[2] != n) return 0.0;
+    const double coef = floor(0.5 + exp(factorial_ln(n) - (factorial_ln(x[0]) + factorial_ln(x[1]) + factorial_ln(x[2]))));
+    double num = 1.0;
+    for (int i = 0; i < 3; i++) num *= pow(p[i], (double)x[i]);
+    return coef * num;
+}
+// MathOperations.PToQ_CapAt300 (a float), and C#'s Math.Min(float, float) / (int) of a double
+PISCES_GHD inline float p_to_q_cap_at_300(double p) { return p < 1e-300 ? 3000.0f : (float)(-10 * log10(p)); }
+PISCES_GHD inline float min_f(float a, float b) { return (a < b || a != a) ? a : b; }
+PISCES_GHD inline int32_t int_of(double v) { return (v > -2147483649.0 && v < 2147483648.0) ? (int32_t)v : INT32_MIN; }
+PISCES_GHD inline int32_t adaptive_q_of(double pWrong)   // Math.Min((int)_maxQScore, (int)Math.Round(PToQ_CapAt300(1 - posterior)))
+{
+    const int32_t q = int_of(rint((double)p_to_q_cap_at_300(pWrong)));
+    return q < 100 ? q : 100;
+}
+// DiploidAdaptiveGenotyper.GetMinVarFrequency: the analytic frequency threshold at depth n (infinite or NaN at n = 0, as in the C#)
+PISCES_GHD inline float adaptive_min_var_frequency(int n, const double model[3], const double priors[3])
+{
+    const double mu1 = model[0], mu2 = model[1], prior1 = priors[0], prior2 = priors[1];
+    const double minVq = (log(prior2) - log(prior1) - n * log(1 - mu1) + n * log(1 - mu2)) / (log(mu1) - log(1 - mu1) - log(mu2) + log(1 - mu2)) / n;
+    return (float)minVq;
+}
+// AdaptiveGenotyperCalculator.PreprocessCalledAllele: allele depth and depth as the mixture sees them (at most 1000)
+PISCES_GHD inline void adaptive_preprocess(bool isReference, int32_t support, int32_t coverage, int& ad, int& dp)
+{
+    dp = coverage;
+    ad = isReference ? (dp - support > 0 ? dp - support : 0) : support;
+    if (dp > 1000) {
+        ad = (int)((double)ad / dp * 1000);
+        dp = 1000;
+    }
+    if (ad > dp) ad = dp;
+}
+// MixtureModel.CalculatePosteriors (:319-346), the Normal.PDF fallback as written
+PISCES_GHD inline void adaptive_posteriors(const int k[3], const int n[3], const double means[3], const double priors[3], double post[3])
+{
+    double temp[3], sum = 0;
+    for (int i = 0; i < 3; i++) {
+        temp[i] = binomial_pmf(means[i], n[i], k[i]) * priors[i];
+        sum += temp[i];
+        if (i == 2 && sum == 0) {
+            for (int ii = 0; ii < 3; ii++) {
+                temp[ii] = normal_pdf(means[ii], sqrt(n[i] * means[ii] * (1 - means[ii])), (double)k[i] / n[i]);
+                sum += temp[ii];
+            }
+        }
+    }
+    for (int i = 0; i < 3; i++) post[i] = temp[i] / sum;
+}
+// MixtureModel.GetSimplifiedGenotype: the first index of the largest posterior (Enumerable.Max passes over NaN; Array.IndexOf)
+PISCES_GHD inline int adaptive_category(int ad, int dp, const double means[3], const double priors[3])
+{
+    const int k[3] = {ad, ad, ad}, n[3] = {dp, dp, dp};
+    double post[3];
+    adaptive_posteriors(k, n, means, priors, post);
+    int cat = 0;
+    for (int i = 1; i < 3; i++)
+        if (post[i] > post[cat] || (post[cat] != post[cat] && post[i] == post[i])) cat = i;
+    return cat;
+}
+// MixtureModel.CalculateQScoreAndGenotypePosteriors (:281-317, 389-406) with the default effective depths {25, 25, 10}: the category, the
+// unclamped q-score, three phred-scaled posteriors
+PISCES_GHD inline int adaptive_qscore_and_posteriors(int ad, int dp, const double means[3], const double priors[3], int32_t& qscore, float gp[3])
+{
+    const int cat = adaptive_category(ad, dp, means, priors);
+    const int maxN[3] = {25, 25, 10};
+    int k[3], n[3];
+    for (int i = 0; i < 3; i++) {
+        if (dp > maxN[i]) {
+            const double vf = (double)ad / dp;
+            k[i] = int_of(rint(vf * maxN[i]));
+            n[i] = maxN[i];
+        } else {
+            k[i] = ad;
+            n[i] = dp;
+        }
+    }
+    double post[3];
+    adaptive_posteriors(k, n, means, priors, post);
+    for (int i = 0; i < 3; i++) gp[i] = min_f(100.0f, p_to_q_cap_at_300(post[i]));
+    qscore = adaptive_q_of(1 - post[cat]);
+    return cat;
+}
+// AdaptiveGenotyperCalculator.GetMultiAllelicQScores + MixtureModel.GetMultinomialQScores: six posteriors and the q-score of a 1/2 locus
+// from its first two alleles (in input order); means1 / means2 are their models
+PISCES_GHD inline void adaptive_multinomial(int32_t support1, int32_t support2, int32_t totalCoverage, const double means1[3], const double means2[3],
+                                            int32_t& qscore, float gp[6])
+{
+    const int dp = totalCoverage;
+    int ad[3];
+    ad[2] = support2;
+    ad[1] = support1;
+    ad[0] = dp - ad[1] - ad[2] > 0 ? dp - ad[1] - ad[2] : 0;
+    if (dp > 500) {   // "Can't be calculated"
+        for (int i = 0; i < 6; i++) gp[i] = i == 4 ? 0.0f : 100.0f;
+        qscore = 100;
+        return;
+    }
+    double temp[6], norm = 0;
+    int count = 0;
+    for (int m2 = 0; m2 < 3; m2++) {
+        for (int m1 = 0; m1 < 3; m1++) {
+            if ((m1 == 2 && m2 != 0) || (m2 == 2 && m1 != 0)) continue;   // either allele hom-alt and the other not hom-ref
+            double p[3];
+            p[1] = means1[m1];
+            p[2] = means2[m2];
+            p[0] = 1 - p[1] - p[2];
+            if (p[0] <= 0) {
+                if (m1 == 2) p[0] = 1 - p[1];
+                else if (m2 == 2) p[0] = 1 - p[2];
+                else if (m1 == 1 && m2 == 1) p[0] = 1 - means1[2];
+            }
+            const double prior = (m1 == 0 && m2 == 0) ? 0.99 : 0.01 / 5;
+            temp[count] = multinomial_probability(p, dp, ad) * prior;
+            norm = norm + temp[count];
+            count++;
+        }
+    }
+    for (int i = 0; i < 6; i++) gp[i] = min_f(100.0f, p_to_q_cap_at_300(temp[i] / norm));
+    qscore = adaptive_q_of(1 - temp[4] / norm);
+}
+// AdaptiveGenotypingParameters.GetModelsAndPriors: SNV / Reference / MNV the SNV pair, insertions / deletions the indel pair
+PISCES_GHD inline const double* adaptive_model_of(const PiscesAdaptiveParams& A, int32_t category)
+{
+    return (category == PISCES_CAT_INSERTION || category == PISCES_CAT_DELETION) ? A.indel_model : A.snv_model;
+}
+PISCES_GHD inline const double* adaptive_prior_of(const PiscesAdaptiveParams& A, int32_t category)
+{
+    return (category == PISCES_CAT_INSERTION || category == PISCES_CAT_DELETION) ? A.indel_prior : A.snv_prior;
+}
+PISCES_GHD inline int32_t clamp_gq(int32_t q, int32_t lo, int32_t hi)   // Math.Max(Math.Min(q, max), min)
+{
+    const int32_t v = q < hi ? q : hi;
+    return v > lo ? v : lo;
+}
+
+// DiploidAdaptiveGenotyper.SetGenotypes over the alleles of one locus, n >= 1, in input order; out[i] receives allele i's posteriors (every
+// allele's, the pruned ones included).  Returns the locus genotype.
+template <typename Before>
+PISCES_GHD inline int32_t adaptive_set(Allele* a, int n, int* order, const PiscesAdaptiveParams& A, int32_t minDepthToGenotype, int32_t minGQ, int32_t maxGQ,
+                                       Before before, PiscesGenotypePosteriors* out)
+{
+    // CalculateDiploidGenotypeFromBinomialModel
+    float minVariantFrequency = adaptive_min_var_frequency(a[0].coverage, A.snv_model, A.snv_prior);
+    double referenceFrequency = 1;   // the genotyper's own GetReferenceFrequency (:146-159)
+    bool sawReference = false;
+    for (int i = 0; i < n && !sawReference; i++) {
+        if (a[i].category == PISCES_CAT_REFERENCE) {
+            referenceFrequency = frequency_of(a[i].support, a[i].coverage);
+            sawReference = true;
+        } else referenceFrequency = referenceFrequency - frequency_of(a[i].support, a[i].coverage);
+    }
+    if (!sawReference) referenceFrequency = referenceFrequency > 0 ? referenceFrequency : 0;
+    bool depthIssue = false;
+    for (int i = 0; i < n; i++) depthIssue |= a[i].coverage < minDepthToGenotype;
+    const bool refExists = referenceFrequency > (double)minVariantFrequency;
+    const int nv = order_by_frequency(a, n, order, minVariantFrequency, before);
+    const bool refCall = nv == 0;
+    int prelim = 0;
+    if (!refCall) {
+        const Allele& d = a[order[0]];
+        const double* model = adaptive_model_of(A, d.category);
+        const double* priors = adaptive_prior_of(A, d.category);
+        int ad, dp;
+        adaptive_preprocess(d.category == PISCES_CAT_REFERENCE, d.support, d.coverage, ad, dp);
+        prelim = adaptive_category(ad, dp, model, priors);
+        minVariantFrequency = adaptive_min_var_frequency(d.coverage, model, priors);
+    }
+    const int32_t gt = complex_genotype(a, n, order, nv, referenceFrequency, refExists, depthIssue, refCall, minVariantFrequency,
+                                        A.sum_vf_for_multi_allelic_site, prelim);
+    prune_beyond_genotype(a, order, nv, gt);
+    // SetGenotypes
+    int phase = 1;
+    for (int i = 0; i < n; i++) {
+        a[i].genotype = gt;
+        PiscesGenotypePosteriors& o = out[i];
+        o.n = 3;
+        o.reserved = 0;
+        o.gp[3] = o.gp[4] = o.gp[5] = 0.0f;
+        if (a[i].coverage == 0) {
+            a[i].genotype_qscore = minGQ;
+            o.gp[0] = o.gp[1] = o.gp[2] = (float)A.max_genotype_posteriors;
+        } else {
+            int ad, dp;
+            adaptive_preprocess(a[i].category == PISCES_CAT_REFERENCE, a[i].support, a[i].coverage, ad, dp);
+            int32_t q;
+            (void)adaptive_qscore_and_posteriors(ad, dp, adaptive_model_of(A, a[i].category), adaptive_prior_of(A, a[i].category), q, o.gp);
+            a[i].genotype_qscore = clamp_gq(q, minGQ, maxGQ);
+        }
+        a[i].phase_set_index = a[i].category == PISCES_CAT_REFERENCE ? 0 : phase++;
+    }
+    if (gt == PISCES_GT_HET_ALT1_ALT2) {   // the multinomial over alleles.First() and alleles.ElementAt(1), for every allele of the locus
+        int32_t q;
+        float gp[6];
+        adaptive_multinomial(a[0].support, a[1].support, a[0].coverage, adaptive_model_of(A, a[0].category), adaptive_model_of(A, a[1].category), q, gp);
+        for (int i = 0; i < n; i++) {
+            a[i].genotype_qscore = clamp_gq(q, minGQ, maxGQ);
+            out[i].n = 6;
+            for (int j = 0; j < 6; j++) out[i].gp[j] = gp[j];
+        }
     }
     return gt;
 }

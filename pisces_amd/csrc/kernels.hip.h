@@ -1496,7 +1496,7 @@ __host__ __device__ inline int candidate_total_coverage(const DevCandidate& c, c
     return spanning_coverage(c, counts, expect_stitched).total;
 }
 
-// PloidyModel.DiploidByThresholding / Haploid over the tile kernels' record slots, lane = locus (AlleleCaller.ComputeGenotypeAndFilterAllele,
+// PloidyModel.DiploidByThresholding / Haploid / DiploidByAdaptiveGT over the tile kernels' record slots, lane = locus (AlleleCaller.ComputeGenotypeAndFilterAllele,
 // AlleleCaller.cs:143-177 with genotype_core.h): the rows of a locus are its valid slots — variants in rank order A C G T, which is their
 // (REF, ALT) order, or the one Reference row —, every kept row gets the locus genotype, its own genotype q-score, the LowGQ and
 // MultiAllelicSite filters and its phase-set index; rows beyond the ploidy lose their validity bit (the compaction that follows never
@@ -1508,8 +1508,12 @@ struct GenotypeParams {
     float snv[3], indel[3];
     int32_t min_depth, min_gq, max_gq, low_gq_filter;
 };
-__global__ __launch_bounds__(64) void genotype_loci_kernel(PiscesCalledAllele* __restrict__ records, PiscesTileResult* __restrict__ tile_results, int32_t n_tiles,
-                                                           GenotypeParams G, unsigned long long* __restrict__ totals)
+// kAdaptive: PloidyModel.DiploidByAdaptiveGT (genotype::adaptive_set with A); the posteriors of every row of the locus go to the
+// slot-parallel `posteriors` (entry = the row's record slot; may be null)
+template <bool kAdaptive>
+__device__ __forceinline__ void genotype_loci_body(PiscesCalledAllele* __restrict__ records, PiscesTileResult* __restrict__ tile_results, int32_t n_tiles,
+                                                   const GenotypeParams& G, unsigned long long* __restrict__ totals, const PiscesAdaptiveParams* A,
+                                                   PiscesGenotypePosteriors* __restrict__ posteriors)
 {
     const int t = blockIdx.x;
     if (t >= n_tiles) return;
@@ -1532,7 +1536,14 @@ __global__ __launch_bounds__(64) void genotype_loci_kernel(PiscesCalledAllele* _
             n++;
         }
         auto before = [](int x, int y) { return x < y; };   // slot rank = ordinal order of the ALT base (one REF base a locus)
-        if (G.ploidy == PISCES_PLOIDY_HAPLOID) (void)genotype::haploid_set(a, n, order, G.snv[0], G.snv[1], G.min_depth, G.min_gq, G.max_gq, before);
+        if constexpr (kAdaptive) {
+            PiscesGenotypePosteriors gp[4];
+            (void)genotype::adaptive_set(a, n, order, *A, G.min_depth, G.min_gq, G.max_gq, before, gp);
+            if (posteriors) {
+                PiscesGenotypePosteriors* const dst = posteriors + (int64_t)t * kSlotsPerTile + l * 4;
+                for (int i = 0; i < n; i++) dst[slot[i]] = gp[i];
+            }
+        } else if (G.ploidy == PISCES_PLOIDY_HAPLOID) (void)genotype::haploid_set(a, n, order, G.snv[0], G.snv[1], G.min_depth, G.min_gq, G.max_gq, before);
         else (void)genotype::diploid_set(a, n, order, G.snv, G.indel, G.min_depth, G.min_gq, G.max_gq, before);
         for (int i = 0; i < n; i++) {
             if (a[i].prune) { keep &= ~(1u << slot[i]); continue; }
@@ -1566,6 +1577,50 @@ __global__ __launch_bounds__(64) void genotype_loci_kernel(PiscesCalledAllele* _
             atomicAdd(&tt[0], (unsigned long long)(long long)(n_now - n_was));
             atomicAdd(&tt[1], (unsigned long long)(long long)(loci_now - loci_was));
         }
+    }
+}
+__global__ __launch_bounds__(64) void genotype_loci_kernel(PiscesCalledAllele* __restrict__ records, PiscesTileResult* __restrict__ tile_results, int32_t n_tiles,
+                                                           GenotypeParams G, unsigned long long* __restrict__ totals)
+{
+    genotype_loci_body<false>(records, tile_results, n_tiles, G, totals, nullptr, nullptr);
+}
+__global__ __launch_bounds__(64) void genotype_loci_adaptive_kernel(PiscesCalledAllele* __restrict__ records, PiscesTileResult* __restrict__ tile_results,
+                                                                    int32_t n_tiles, GenotypeParams G, PiscesAdaptiveParams A,
+                                                                    PiscesGenotypePosteriors* __restrict__ posteriors, unsigned long long* __restrict__ totals)
+{
+    genotype_loci_body<true>(records, tile_results, n_tiles, G, totals, &A, posteriors);
+}
+// The posteriors of a launch's valid slots in the order of its compacted records: out[offsets[t] + rank of the slot in tile t], offsets as
+// the record compaction of the same directory left them (gather_records_kernel's walk over the slot-parallel buffer); offsets == nullptr:
+// the tile's wave adds up the record counts of the tiles before it, as gather_direct_kernel does
+__global__ __launch_bounds__(64) void gather_posteriors_kernel(const PiscesGenotypePosteriors* __restrict__ posteriors, const PiscesTileResult* __restrict__ tr,
+                                                               int32_t n_tiles, const int32_t* __restrict__ offsets,
+                                                               PiscesGenotypePosteriors* __restrict__ out, int32_t capacity)
+{
+    const int t = blockIdx.x;
+    if (t >= n_tiles) return;
+    const int l = threadIdx.x;
+    const uint32_t nib = (tr[t].valid[l >> 3] >> ((l & 7) * 4)) & 0xFu;
+    int x = __popc(nib);
+    const int mine = x;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        int y = __shfl_up(x, d, 64);
+        if (l >= d) x += y;
+    }
+    int base = 0;
+    if (offsets) base = offsets[t];
+    else {
+        for (int i = l; i < t; i += 64) base += tr[i].n_records;
+#pragma unroll
+        for (int d = 32; d > 0; d >>= 1) base += __shfl_xor(base, d, 64);
+    }
+    int64_t dst = (int64_t)base + (x - mine);
+    const PiscesGenotypePosteriors* src = posteriors + (int64_t)t * kSlotsPerTile + l * 4;
+    for (int k = 0; k < 4; k++) {
+        if (!(nib & (1u << k))) continue;
+        if (dst >= 0 && dst < capacity) out[dst] = src[k];
+        dst++;
     }
 }
 

@@ -330,6 +330,7 @@ struct PiscesHip {
     DeviceBuf<long long> d_summary;
     DeviceBuf<int32_t> d_offsets;
     DeviceBuf<PiscesCalledAllele> d_compact;
+    DeviceBuf<PiscesGenotypePosteriors> d_post, d_post_compact;   // PloidyModel.DiploidByAdaptiveGT: slot-parallel to d_records / row-parallel to d_compact + 1
     int kernel_variant = 4;    // 4 = auto (two waves per tile while every tile of the launch is resident at once, else one),
                                // 2 = one wave per tile, 3 = two waves per tile, 0 = one 4-wave workgroup per tile
     std::string err;
@@ -376,6 +377,7 @@ struct PiscesHip {
         size_t n_view = 0;
         std::vector<PiscesCalledAllele> rows;
         std::vector<int32_t> index;            // per row: index into cands, -1 for Reference / SNV rows (empty: a batch the device called alone)
+        std::vector<PiscesGenotypePosteriors> posteriors;   // per row, PloidyModel.DiploidByAdaptiveGT (empty: no row has any)
         std::vector<HostCandidate> cands;      // the called insertion / deletion / MNV candidates (their allele strings)
         std::vector<PiscesCandidate> exported; // cands and their allele strings as the views hand them out
         std::vector<uint8_t> alleles;
@@ -390,7 +392,7 @@ struct PiscesHip {
             valid = dropped = false;
             view = nullptr;
             n_view = 0;
-            rows.clear(); index.clear(); cands.clear(); exported.clear(); alleles.clear(); keys.clear();
+            rows.clear(); index.clear(); posteriors.clear(); cands.clear(); exported.clear(); alleles.clear(); keys.clear();
             called = collapsed = 0;
             kept = 0;
         }
@@ -443,6 +445,8 @@ struct PiscesHip {
     uint8_t* h_meta = nullptr;
     size_t h_meta_cap = 0, h_meta_used = 0;
     size_t h_dl_cap = 0;
+    PiscesGenotypePosteriors* h_post = nullptr;   // pinned: the compacted posteriors of a flush the device genotyped (row-parallel to h_dl + 1)
+    size_t h_post_cap = 0;                        // entries
     bool drop_counter_cleared = false;   // d_log_n[log_cur ^ 1] was zeroed by the last bucket_scan_kernel and not used since
     DeviceBuf<long long> d_total;
 
@@ -554,6 +558,9 @@ struct PiscesHip {
                                               // inside small groups (exchanged_tile), or position order (PISCES_HIP_TILE_ORDER=0)
     bool finder_bases = false;                // PISCES_HIP_FINDER=bases: the candidate walk a lane a read, base by base (round 3's), not events first
     DeviceBuf<long long> d_scan_sums;         // block sums of launch_found_scan
+    PiscesAdaptiveParams adaptive;            // PloidyModel.DiploidByAdaptiveGT: the mixture's means and priors (pisces_hip_set_adaptive_params)
+    PiscesGenotypePosteriors* d_posteriors = nullptr;   // pisces_hip_set_posteriors_buffer: slot-parallel to the d_records of pisces_hip_call_tiles
+    int64_t posteriors_capacity = 0;
     bool device_genotyper = true;             // PISCES_HIP_DEVICE_GENOTYPER=0: diploid / haploid genotypes are always the host pass of the flush (the A / B of the tests)
     bool merge_in_place = true;               // PISCES_HIP_MERGE_IN_PLACE=0: the candidate kernel's rows and the tile kernels' are merged into a vector of their own (the A / B of the tests)
     int device_checks = -1;                   // PISCES_HIP_DEVICE_CHECKS: 1 every host batch is checked on the device (add_fused_kernel), 0 none, -1 (default) from 65 536 reads up
@@ -852,7 +859,7 @@ int32_t pisces_hip_create(const PiscesHipConfig* cfg, int32_t device, PiscesHip*
     if (cfg->tile_loci != 0 && cfg->tile_loci != kTile)
         return fail(nullptr, PISCES_E_UNSUPPORTED, "pisces_hip_create: tile_loci must be 64 in this build");
     if (cfg->strand_bias_model < PISCES_SB_POISSON || cfg->strand_bias_model > PISCES_SB_DIPLOID || cfg->ploidy < PISCES_PLOIDY_SOMATIC ||
-        cfg->ploidy > PISCES_PLOIDY_HAPLOID || cfg->noise_model < PISCES_NOISE_FLAT || cfg->noise_model > PISCES_NOISE_WINDOW)
+        cfg->ploidy > PISCES_PLOIDY_DIPLOID_ADAPTIVE || cfg->noise_model < PISCES_NOISE_FLAT || cfg->noise_model > PISCES_NOISE_WINDOW)
         return fail(nullptr, PISCES_E_INVALID_ARG, "pisces_hip_create: strand_bias_model / ploidy / noise_model out of range");
     if (cfg->block_size <= 0 || cfg->min_base_call_quality < 0 || cfg->min_base_call_quality > 254)
         return fail(nullptr, PISCES_E_INVALID_ARG, "pisces_hip_create: block_size / min_base_call_quality out of range");
@@ -865,6 +872,7 @@ int32_t pisces_hip_create(const PiscesHipConfig* cfg, int32_t device, PiscesHip*
     h->cfg = *cfg;
     h->cfg.tile_loci = kTile;
     h->P = make_params(h->cfg);
+    adaptive_default_params(h->adaptive);
     h->device = device;
     if ((e = hipSetDevice(device)) != hipSuccess || (e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking)) != hipSuccess ||
         (e = hipEventCreate(&h->ev0)) != hipSuccess || (e = hipEventCreate(&h->ev1)) != hipSuccess) {
@@ -1061,7 +1069,7 @@ int32_t pisces_hip_destroy(PiscesHip* h)
     }
     h->d_summary.release();
     h->d_ref.release(); h->d_tuples.release(); h->d_tiles.release(); h->d_tile_results.release();
-    h->d_records.release(); h->d_counts.release(); h->d_gapped.release(); h->d_count.release(); h->d_totals.release(); h->d_qlut.release(); h->d_bq_lut.release(); h->d_sumq_fix.release(); h->d_sumq.release(); h->d_gq_tail.release(); h->d_vq_tab.release(); h->d_sb_tab.release(); h->d_sb0_tab.release(); h->d_gq_cap.release(); h->d_params.release(); h->d_offsets.release(); h->d_compact.release();
+    h->d_records.release(); h->d_counts.release(); h->d_gapped.release(); h->d_count.release(); h->d_totals.release(); h->d_qlut.release(); h->d_bq_lut.release(); h->d_sumq_fix.release(); h->d_sumq.release(); h->d_gq_tail.release(); h->d_vq_tab.release(); h->d_sb_tab.release(); h->d_sb0_tab.release(); h->d_gq_cap.release(); h->d_params.release(); h->d_offsets.release(); h->d_compact.release(); h->d_post.release(); h->d_post_compact.release();
     for (int i = 0; i < 2; i++) { h->d_log_pos[i].release(); h->d_log_tup[i].release(); }
     h->d_log_n.release(); h->d_flags.release(); h->d_bucket.release(); h->d_total.release();
     for (auto& st : h->stage) {
@@ -1076,6 +1084,8 @@ int32_t pisces_hip_destroy(PiscesHip* h)
     h->async.done = nullptr;
     if (h->h_dl) host_free(h->h_dl);
     h->h_dl = nullptr;
+    if (h->h_post) host_free(h->h_post);
+    h->h_post = nullptr;
     if (h->h_cand_dl) host_free(h->h_cand_dl);
     h->h_cand_dl = nullptr;
     if (h->h_meta) host_free(h->h_meta);

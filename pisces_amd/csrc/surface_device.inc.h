@@ -16,6 +16,8 @@ int32_t pisces_hip_call_tiles(PiscesHip* h, const uint32_t* d_tuples, const Pisc
         return fail(h, PISCES_E_INVALID_ARG, "call_tiles: null device pointer");
     if ((int64_t)record_capacity < (int64_t)n_tiles * kSlotsPerTile)
         return fail(h, PISCES_E_BUFFER_TOO_SMALL, "call_tiles: the slot layout needs record_capacity >= 256 * n_tiles");
+    if (h->d_posteriors && h->posteriors_capacity < (int64_t)n_tiles * kSlotsPerTile)
+        return fail(h, PISCES_E_BUFFER_TOO_SMALL, "call_tiles: the posteriors buffer (pisces_hip_set_posteriors_buffer) needs 256 * n_tiles entries");
     PISCES_HIP_CHECK(h, hipSetDevice(h->device));
     hipStream_t s = stream ? (hipStream_t)stream : h->stream;
     if (s != h->stream) h->foreign_stream_used = h->foreign_stream_ever = true;
@@ -30,7 +32,8 @@ int32_t pisces_hip_call_tiles(PiscesHip* h, const uint32_t* d_tuples, const Pisc
     }
     if (n_tiles > 0) {
         PISCES_HIP_CHECK(h, launch_call_tiles(h, s, d_tuples, d_tiles, n_tiles, d_ref_bases, ref_start_position, ref_length, d_records, d_tile_results, e0, e1));
-        if (germline(h)) launch_genotype_loci(h, s, d_records, d_tile_results, n_tiles);   // PloidyModel.DiploidByThresholding / Haploid: a pass over the slots
+        // PloidyModel.DiploidByThresholding / Haploid / DiploidByAdaptiveGT: a pass over the slots
+        if (germline(h)) launch_genotype_loci(h, s, d_records, d_tile_results, n_tiles, h->d_posteriors);
     } else if (e0) {
         PISCES_HIP_CHECK(h, hipEventRecord(e0, s));
         PISCES_HIP_CHECK(h, hipEventRecord(e1, s));
@@ -62,6 +65,8 @@ int32_t pisces_hip_call_tiles_batched(PiscesHip* h, const PiscesTileBatch* batch
     return abi_guard<int32_t>(h, [&]() -> int32_t {
     if (!h) return PISCES_E_INVALID_ARG;
     if (n_batches < 0 || (n_batches > 0 && !batches)) return fail(h, PISCES_E_INVALID_ARG, "call_tiles_batched: null batch list");
+    if (h->cfg.ploidy == PISCES_PLOIDY_DIPLOID_ADAPTIVE)
+        return fail(h, PISCES_E_UNSUPPORTED, "call_tiles_batched: PloidyModel.DiploidByAdaptiveGT has one posteriors buffer a handle; use pisces_hip_call_tiles");
     if (h->cfg.noise_model == PISCES_NOISE_WINDOW)
         return fail(h, PISCES_E_STATE, "call_tiles_batched: NoiseModel.Window calls through the handle's one counts tensor; use pisces_hip_call_tiles");
     for (int32_t i = 0; i < n_batches; i++) {
@@ -101,6 +106,8 @@ int32_t pisces_hip_call_tiles_graph_build(PiscesHip* h, const PiscesTileBatch* b
     return abi_guard<int32_t>(h, [&]() -> int32_t {
     if (!h || !graph_id) return PISCES_E_INVALID_ARG;
     if (n_batches <= 0 || !batches) return fail(h, PISCES_E_INVALID_ARG, "call_tiles_graph_build: null batch list");
+    if (h->cfg.ploidy == PISCES_PLOIDY_DIPLOID_ADAPTIVE)
+        return fail(h, PISCES_E_UNSUPPORTED, "call_tiles_graph_build: PloidyModel.DiploidByAdaptiveGT has one posteriors buffer a handle; use pisces_hip_call_tiles");
     if (h->cfg.noise_model == PISCES_NOISE_WINDOW)
         return fail(h, PISCES_E_STATE, "call_tiles_graph_build: NoiseModel.Flat only (see pisces_hip_call_tiles_batched)");
     for (int32_t i = 0; i < n_batches; i++) {
@@ -180,6 +187,35 @@ int32_t pisces_hip_compact_records(PiscesHip* h, const PiscesCalledAllele* d_rec
         return PISCES_OK;
     }
     { int32_t rcc = launch_compaction(h, s, d_records, d_tile_results, n_tiles, d_offsets, d_out, out_capacity, d_count); if (rcc) return rcc; }
+    PISCES_HIP_CHECK(h, hipGetLastError());
+    return PISCES_OK;
+    });
+}
+
+int32_t pisces_hip_set_posteriors_buffer(PiscesHip* h, PiscesGenotypePosteriors* d_posteriors, int64_t capacity)
+{
+    return abi_guard<int32_t>(h, [&]() -> int32_t {
+    if (!h) return PISCES_E_INVALID_ARG;
+    if (capacity < 0 || (capacity > 0 && !d_posteriors)) return fail(h, PISCES_E_INVALID_ARG, "set_posteriors_buffer: null device pointer");
+    if (h->cfg.ploidy != PISCES_PLOIDY_DIPLOID_ADAPTIVE) return fail(h, PISCES_E_STATE, "set_posteriors_buffer: the handle's ploidy is not PISCES_PLOIDY_DIPLOID_ADAPTIVE");
+    h->d_posteriors = capacity > 0 ? d_posteriors : nullptr;
+    h->posteriors_capacity = capacity;
+    return PISCES_OK;
+    });
+}
+
+int32_t pisces_hip_compact_posteriors(PiscesHip* h, const PiscesGenotypePosteriors* d_posteriors, const PiscesTileResult* d_tile_results, int32_t n_tiles,
+                                      const int32_t* d_offsets, PiscesGenotypePosteriors* d_out, int32_t out_capacity, void* stream)
+{
+    return abi_guard<int32_t>(h, [&]() -> int32_t {
+    if (!h) return PISCES_E_INVALID_ARG;
+    if (n_tiles < 0 || out_capacity < 0) return fail(h, PISCES_E_INVALID_ARG, "compact_posteriors: negative size");
+    if (n_tiles > 0 && (!d_posteriors || !d_tile_results || !d_offsets || !d_out)) return fail(h, PISCES_E_INVALID_ARG, "compact_posteriors: null device pointer");
+    if (n_tiles == 0) return PISCES_OK;
+    PISCES_HIP_CHECK(h, hipSetDevice(h->device));
+    hipStream_t s = stream ? (hipStream_t)stream : h->stream;
+    if (s != h->stream) h->foreign_stream_used = h->foreign_stream_ever = true;
+    hipLaunchKernelGGL(gather_posteriors_kernel, dim3((unsigned)n_tiles), dim3(64), 0, s, d_posteriors, d_tile_results, n_tiles, d_offsets, d_out, out_capacity);
     PISCES_HIP_CHECK(h, hipGetLastError());
     return PISCES_OK;
     });

@@ -216,8 +216,10 @@ static hipError_t launch_call_tiles(PiscesHip* h, hipStream_t s, const uint32_t*
     return hipSuccess;
 }
 
-// PloidyModel.DiploidByThresholding / Haploid over the record slots a tile kernel has just filled (genotype_loci_kernel), on stream s
-static void launch_genotype_loci(PiscesHip* h, hipStream_t s, PiscesCalledAllele* d_records, PiscesTileResult* d_tr, int32_t n_tiles)
+// PloidyModel.DiploidByThresholding / Haploid / DiploidByAdaptiveGT over the record slots a tile kernel has just filled (genotype_loci_kernel,
+// genotype_loci_adaptive_kernel), on stream s
+static void launch_genotype_loci(PiscesHip* h, hipStream_t s, PiscesCalledAllele* d_records, PiscesTileResult* d_tr, int32_t n_tiles,
+                                 PiscesGenotypePosteriors* d_posteriors = nullptr)
 {
     GenotypeParams G;
     G.ploidy = h->cfg.ploidy;
@@ -226,9 +228,15 @@ static void launch_genotype_loci(PiscesHip* h, hipStream_t s, PiscesCalledAllele
     G.min_gq = h->cfg.min_genotype_qscore;
     G.max_gq = h->cfg.max_genotype_qscore;
     G.low_gq_filter = h->cfg.low_gq_filter;
-    if (n_tiles > 0) hipLaunchKernelGGL(genotype_loci_kernel, dim3((unsigned)n_tiles), dim3(64), 0, s, d_records, d_tr, n_tiles, G, h->P.totals);
+    if (n_tiles <= 0) return;
+    if (h->cfg.ploidy == PISCES_PLOIDY_DIPLOID_ADAPTIVE)   // the posteriors go to the slot-parallel buffer when d_records is the one it was named for
+        hipLaunchKernelGGL(genotype_loci_adaptive_kernel, dim3((unsigned)n_tiles), dim3(64), 0, s, d_records, d_tr, n_tiles, G, h->adaptive, d_posteriors, h->P.totals);
+    else hipLaunchKernelGGL(genotype_loci_kernel, dim3((unsigned)n_tiles), dim3(64), 0, s, d_records, d_tr, n_tiles, G, h->P.totals);
 }
-static bool germline(const PiscesHip* h) { return h->cfg.ploidy == PISCES_PLOIDY_DIPLOID || h->cfg.ploidy == PISCES_PLOIDY_HAPLOID; }
+static bool germline(const PiscesHip* h)
+{
+    return h->cfg.ploidy == PISCES_PLOIDY_DIPLOID || h->cfg.ploidy == PISCES_PLOIDY_HAPLOID || h->cfg.ploidy == PISCES_PLOIDY_DIPLOID_ADAPTIVE;
+}
 
 // scan + gather: d_out = called alleles in (position, allele) order, *d_count = how many
 // ONE launch: gather_direct_kernel up to kGatherDirectTiles tiles (a tile's wave adds up the counts before it), compact_records_kernel beyond
@@ -273,6 +281,7 @@ struct CallBlocksInFlight {
     int32_t* hdr = nullptr;
     PiscesCalledAllele* hrec = nullptr;
     size_t spec = 0;
+    bool posteriors = false;          // the rows' posteriors come back too (h->h_post)
     const int32_t* extra = nullptr;   // {records, called} of the counting launch over the off-interval loci (exact TotalNumCalled), or nullptr
 };
 // pisces_hip_set_exact_total_called: the loci of `keys`' blocks that lie OUTSIDE the interval set, through the flush kernel once more with
@@ -432,7 +441,12 @@ static int32_t call_blocks_enqueue(PiscesHip* h, const std::vector<int32_t>& key
                            h->d_tiles.p, n_tiles, h->d_ref.p, 1, h->ref_len, h->d_records.p, h->d_tile_results.p, h->P,
                            window ? h->d_sumq.p : (const double*)nullptr);
     }
-    if (genotype_on_device) launch_genotype_loci(h, h->stream, h->d_records.p, h->d_tile_results.p, n_tiles);
+    const bool with_posteriors = genotype_on_device && h->cfg.ploidy == PISCES_PLOIDY_DIPLOID_ADAPTIVE;
+    if (with_posteriors) {
+        PISCES_HIP_CHECK(h, h->d_post.reserve(cap));
+        PISCES_HIP_CHECK(h, h->d_post_compact.reserve(cap));
+    }
+    if (genotype_on_device) launch_genotype_loci(h, h->stream, h->d_records.p, h->d_tile_results.p, n_tiles, with_posteriors ? h->d_post.p : nullptr);
     // tiles were built in ascending position order: the ordered compaction is AlleleCaller.Call's (position, ref, alt) order.
     // The sorted records lie behind one header slot {records, called}.  A launch of up to 64 tiles (the blocks of one flush of the
     // streaming protocol) is compacted by one kernel that writes header and records into the pinned download buffer itself.
@@ -466,6 +480,21 @@ static int32_t call_blocks_enqueue(PiscesHip* h, const std::vector<int32_t>& key
         PISCES_HIP_CHECK(h, hipMemcpyAsync(hdr, h->d_count.p, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
         PISCES_HIP_CHECK(h, hipMemcpyAsync(hrec, h->d_compact.p + 1, spec * sizeof(PiscesCalledAllele), hipMemcpyDeviceToHost, h->stream));
     }
+    if (with_posteriors) {
+        // the posteriors follow their rows: the same order (the small launch's compaction leaves no offsets: the waves add up the directory)
+        // and the same way to the host: a small launch's straight into pinned memory, else the same speculative prefix
+        if (cap > h->h_post_cap) {
+            if (h->h_post) host_free(h->h_post);
+            h->h_post = nullptr;
+            h->h_post_cap = 0;
+            PISCES_HIP_CHECK(h, host_alloc((void**)&h->h_post, (cap + cap / 2) * sizeof(PiscesGenotypePosteriors)));
+            h->h_post_cap = cap + cap / 2;
+        }
+        hipLaunchKernelGGL(gather_posteriors_kernel, dim3((unsigned)n_tiles), dim3(64), 0, h->stream, (const PiscesGenotypePosteriors*)h->d_post.p,
+                           (const PiscesTileResult*)h->d_tile_results.p, n_tiles, small ? (const int32_t*)nullptr : (const int32_t*)h->d_offsets.p,
+                           small ? h->h_post : h->d_post_compact.p, (int32_t)cap);
+        if (!small) PISCES_HIP_CHECK(h, hipMemcpyAsync(h->h_post, h->d_post_compact.p, spec * sizeof(PiscesGenotypePosteriors), hipMemcpyDeviceToHost, h->stream));
+    }
     PISCES_HIP_CHECK(h, hipGetLastError());
     if (drop_now) {
         int32_t rcd = enqueue_drop(h, keys, hole_bound);
@@ -478,6 +507,7 @@ static int32_t call_blocks_enqueue(PiscesHip* h, const std::vector<int32_t>& key
     st->hdr = hdr;
     st->hrec = hrec;
     st->spec = spec;
+    st->posteriors = with_posteriors;
     // pisces_hip_set_exact_total_called: with an interval set and the SNVs taken from the allele counts (MNV calling and collapsing off:
     // otherwise they are candidates, and the candidate path counts the callable ones outside the intervals itself) the off-interval loci
     // get a counting launch of the flush kernel.  A configuration that kernel does not serve cannot give the reference's number: refused
@@ -519,6 +549,9 @@ static int32_t call_blocks_finish(PiscesHip* h, const CallBlocksInFlight& st, in
     if ((size_t)*total > st.spec) {
         PISCES_HIP_CHECK(h, hipMemcpyAsync(st.hrec + st.spec, h->d_compact.p + 1 + st.spec, ((size_t)*total - st.spec) * sizeof(PiscesCalledAllele),
                                            hipMemcpyDeviceToHost, h->stream));
+        if (st.posteriors)
+            PISCES_HIP_CHECK(h, hipMemcpyAsync(h->h_post + st.spec, h->d_post_compact.p + st.spec, ((size_t)*total - st.spec) * sizeof(PiscesGenotypePosteriors),
+                                               hipMemcpyDeviceToHost, h->stream));
         PISCES_HIP_CHECK(h, hipStreamSynchronize(h->stream));
     }
     return PISCES_OK;
@@ -2055,8 +2088,15 @@ static void merge_rows(PiscesHip* h, PiscesHip::FlushResult& r, const std::vecto
 // locus, alleles beyond the ploidy dropped, every kept allele gets its own diploid genotype q-score, LowGQ and MultiAllelicSite filters; the
 // device's somatic genotype fields are replaced.  (Reference rows at variant loci are gone already, rows are in (ref, alt) order.)  The rows
 // that stay move to the front; returns their number.
-static size_t genotype_rows(PiscesHip* h, PiscesCalledAllele* rows, int32_t* index, size_t n, const std::vector<HostCandidate>& cands)
+// PloidyModel.DiploidByAdaptiveGT: DiploidAdaptiveGenotyper the same way, no DiploidLocusProcessor step (Factory.cs:128-147: SomaticLocusProcessor);
+// post[i] receives row i's posteriors (n = 0 for a row the genotyper was not shown) and moves with the row.
+static size_t genotype_rows(PiscesHip* h, PiscesCalledAllele* rows, int32_t* index, size_t n, const std::vector<HostCandidate>& cands,
+                            std::vector<PiscesGenotypePosteriors>& post)
 {
+    const bool adaptive = h->cfg.ploidy == PISCES_PLOIDY_DIPLOID_ADAPTIVE;
+    std::vector<PiscesGenotypePosteriors> at_post;
+    post.clear();
+    if (adaptive) post.assign(n, PiscesGenotypePosteriors{});
     auto ref_at = [&](size_t k) { return index[k] >= 0 ? cands[(size_t)index[k]].ref : ref_of(rows[k]); };
     auto alt_at = [&](size_t k) { return index[k] >= 0 ? cands[(size_t)index[k]].alt : alt_of(rows[k]); };
     std::vector<DiploidAllele> at;
@@ -2079,7 +2119,10 @@ static size_t genotype_rows(PiscesHip* h, PiscesCalledAllele* rows, int32_t* ind
             at.push_back(std::move(a));
             at_row.push_back(k);
         }
-        if (h->cfg.ploidy == PISCES_PLOIDY_HAPLOID)
+        if (adaptive) {
+            if (!at.empty())
+                (void)adaptive_set_genotypes(at, h->adaptive, h->cfg.min_coverage, h->cfg.min_genotype_qscore, h->cfg.max_genotype_qscore, at_post);
+        } else if (h->cfg.ploidy == PISCES_PLOIDY_HAPLOID)
             (void)haploid_set_genotypes(at, h->cfg.diploid_snv_params[0], h->cfg.diploid_snv_params[1], h->cfg.min_coverage,
                                         h->cfg.min_genotype_qscore, h->cfg.max_genotype_qscore);
         else
@@ -2089,7 +2132,9 @@ static size_t genotype_rows(PiscesHip* h, PiscesCalledAllele* rows, int32_t* ind
         size_t ai = 0;
         for (size_t k = i; k < j; k++) {
             PiscesCalledAllele r = rows[k];
+            PiscesGenotypePosteriors gp{};
             if (ai < at_row.size() && at_row[ai] == k) {
+                if (adaptive) gp = at_post[ai];
                 const DiploidAllele& a = at[ai++];
                 // an allele beyond the ploidy goes, unless it is a forced allele (:155-163)
                 if (a.prune && !(!h->forced_keys.empty() && h->forced_keys.count(forced_key(r.position, a.ref, a.alt)))) continue;
@@ -2103,6 +2148,7 @@ static size_t genotype_rows(PiscesHip* h, PiscesCalledAllele* rows, int32_t* ind
             }
             rows[out] = r;
             index[out] = index[k];
+            if (adaptive) post[out] = gp;
             out++;
         }
         if (h->cfg.ploidy == PISCES_PLOIDY_DIPLOID && !h->forced.empty()) {
@@ -2131,6 +2177,7 @@ static size_t genotype_rows(PiscesHip* h, PiscesCalledAllele* rows, int32_t* ind
         }
         i = j;
     }
+    if (adaptive) post.resize(out);
     return out;
 }
 
@@ -2191,12 +2238,13 @@ static int32_t flush_build(PiscesHip* h, int32_t up_to_position, PiscesHip::Flus
         r.dropped = st.drop_now;
         r.view = st.hrec;   // (the pinned download buffer: valid until the next call_blocks_enqueue)
         r.n_view = (size_t)total;
+        if (st.posteriors) r.posteriors.assign(h->h_post, h->h_post + total);   // (nothing joins these rows: the merge below leaves them where they are)
     }
     prof.reset();
     prof.reset(new HostTimer(h->prof_on ? &h->prof[8] : nullptr));
     merge_rows(h, r, span_recs, ref_overrides, host_genotyper || !h->forced.empty());
     if (host_genotyper) {
-        const size_t n = genotype_rows(h, r.view ? r.view : r.rows.data(), r.index.data(), r.size(), r.cands);
+        const size_t n = genotype_rows(h, r.view ? r.view : r.rows.data(), r.index.data(), r.size(), r.cands, r.posteriors);
         if (r.view) r.n_view = n;
         else r.rows.resize(n);
         r.index.resize(n);
@@ -2763,6 +2811,102 @@ int32_t pisces_hip_set_genotypes(const PiscesHipConfig* cfg, PiscesGenotypeAllel
         a[i].multi_allelic = d.multi_allelic ? 1 : 0; a[i].prune = d.prune ? 1 : 0;
     }
     return gt;
+    });
+}
+
+// ---- PloidyModel.DiploidByAdaptiveGT ------------------------------------------------------------------------------------------------
+int32_t pisces_hip_adaptive_default_params(PiscesAdaptiveParams* params)
+{
+    if (!params) return PISCES_E_INVALID_ARG;
+    adaptive_default_params(*params);
+    return PISCES_OK;
+}
+
+int32_t pisces_hip_set_adaptive_params(PiscesHip* h, const PiscesAdaptiveParams* params)
+{
+    return abi_guard<int32_t>(h, [&]() -> int32_t {
+    if (!h) return PISCES_E_INVALID_ARG;
+    if (!params) return fail(h, PISCES_E_INVALID_ARG, "set_adaptive_params: null argument");
+    if (h->cfg.ploidy != PISCES_PLOIDY_DIPLOID_ADAPTIVE) return fail(h, PISCES_E_STATE, "set_adaptive_params: the handle's ploidy is not PISCES_PLOIDY_DIPLOID_ADAPTIVE");
+    if (!adaptive_params_valid(*params))
+        return fail(h, PISCES_E_INVALID_ARG, "set_adaptive_params: means and priors must lie inside (0, 1), the means of a model ascending");
+    h->adaptive = *params;
+    return PISCES_OK;
+    });
+}
+
+int32_t pisces_hip_set_genotypes_adaptive(const PiscesHipConfig* cfg, const PiscesAdaptiveParams* params, PiscesGenotypeAllele* a, int32_t n, const uint8_t* alleles,
+                                          int64_t allele_bytes, PiscesGenotypePosteriors* posteriors_out)
+{
+    return abi_guard<int32_t>((PiscesHip*)nullptr, [&]() -> int32_t {
+    if (!cfg || !params || n < 1 || !a || !adaptive_params_valid(*params)) return PISCES_E_INVALID_ARG;
+    std::vector<DiploidAllele> at((size_t)n);
+    for (int32_t i = 0; i < n; i++) {
+        const PiscesGenotypeAllele& x = a[i];
+        if (x.ref_len < 0 || x.alt_len < 0 || x.allele_offset < 0 || x.allele_offset + x.ref_len + x.alt_len > allele_bytes || (x.ref_len + x.alt_len > 0 && !alleles)) return PISCES_E_INVALID_ARG;
+        if (x.category < PISCES_CAT_SNV || x.category > PISCES_CAT_REFERENCE || x.support < 0 || x.coverage < 0) return PISCES_E_INVALID_ARG;
+        DiploidAllele& d = at[(size_t)i];
+        d.category = x.category;
+        d.ref.assign((const char*)alleles + x.allele_offset, (size_t)x.ref_len);
+        d.alt.assign((const char*)alleles + x.allele_offset + x.ref_len, (size_t)x.alt_len);
+        d.support = x.support; d.coverage = x.coverage; d.ref_support = x.reference_support;
+    }
+    std::vector<PiscesGenotypePosteriors> post;
+    const int32_t gt = adaptive_set_genotypes(at, *params, cfg->min_coverage, cfg->min_genotype_qscore, cfg->max_genotype_qscore, post);
+    for (int32_t i = 0; i < n; i++) {
+        const DiploidAllele& d = at[(size_t)i];
+        a[i].genotype = d.genotype; a[i].genotype_qscore = d.genotype_qscore; a[i].phase_set_index = d.phase_set_index;
+        a[i].multi_allelic = d.multi_allelic ? 1 : 0; a[i].prune = d.prune ? 1 : 0;
+        if (posteriors_out) posteriors_out[i] = post[(size_t)i];
+    }
+    return gt;
+    });
+}
+
+int32_t pisces_hip_adaptive_genotype_qscore(const PiscesAdaptiveParams* params, int32_t category, int32_t is_reference, int32_t allele_support,
+                                            int32_t total_coverage, int32_t* category_out, int32_t* qscore_out, float* gp_out)
+{
+    return abi_guard<int32_t>((PiscesHip*)nullptr, [&]() -> int32_t {
+    if (!params || !category_out || !qscore_out || !gp_out || !adaptive_params_valid(*params) || category < PISCES_CAT_SNV || category > PISCES_CAT_REFERENCE ||
+        allele_support < 0 || total_coverage < 1)
+        return PISCES_E_INVALID_ARG;
+    *category_out = adaptive_genotype_qscore(*params, category, is_reference != 0, allele_support, total_coverage, qscore_out, gp_out);
+    return PISCES_OK;
+    });
+}
+
+// The posteriors of h->result's rows (row i <-> entry i); a flush that made none: n = 0 entries
+static const PiscesGenotypePosteriors* result_posteriors(PiscesHip* h, size_t n)
+{
+    PiscesHip::FlushResult& r = h->result;
+    if (r.posteriors.size() != n) r.posteriors.assign(n, PiscesGenotypePosteriors{});
+    return r.posteriors.data();
+}
+
+int32_t pisces_hip_get_posteriors(PiscesHip* h, PiscesGenotypePosteriors* out, int64_t capacity, int64_t* n_out)
+{
+    return abi_guard<int32_t>(h, [&]() -> int32_t {
+    if (!h) return PISCES_E_INVALID_ARG;
+    if (!n_out || capacity < 0 || (capacity > 0 && !out)) return fail(h, PISCES_E_INVALID_ARG, "get_posteriors: null output");
+    if (h->async.state == 1) return fail(h, PISCES_E_STATE, "get_posteriors: pisces_hip_flush_begin is waiting for its pisces_hip_flush_end");
+    const size_t n = h->result.size();
+    *n_out = (int64_t)n;
+    if ((int64_t)n > capacity) return fail(h, PISCES_E_BUFFER_TOO_SMALL, "get_posteriors: output buffer too small");
+    if (n) std::memcpy(out, result_posteriors(h, n), n * sizeof(PiscesGenotypePosteriors));
+    return PISCES_OK;
+    });
+}
+
+int32_t pisces_hip_posteriors_view(PiscesHip* h, const PiscesGenotypePosteriors** rows, int64_t* n_rows)
+{
+    return abi_guard<int32_t>(h, [&]() -> int32_t {
+    if (!h) return PISCES_E_INVALID_ARG;
+    if (!rows || !n_rows) return fail(h, PISCES_E_INVALID_ARG, "posteriors_view: null output");
+    if (h->async.state == 1) return fail(h, PISCES_E_STATE, "posteriors_view: pisces_hip_flush_begin is waiting for its pisces_hip_flush_end");
+    const size_t n = h->result.size();
+    *rows = n ? result_posteriors(h, n) : nullptr;
+    *n_rows = (int64_t)n;
+    return PISCES_OK;
     });
 }
 

@@ -130,11 +130,11 @@ int32_t pisces_hip_vcf_default_config(PiscesVcfConfig* c)
     return PISCES_OK;
 }
 
-int64_t pisces_hip_format_vcf_padded(const PiscesVcfConfig* cfg, const char* chrom, const PiscesCalledAllele* recs, int64_t n,
-                                     const int32_t* cand_index, const PiscesCandidate* cands, const uint8_t* alleles,
-                                     const uint8_t* ref_bases, int64_t ref_len, const int32_t* interval_starts,
-                                     const int32_t* interval_ends, int32_t n_intervals, PiscesVcfPadState* state, int32_t finish,
-                                     char* out, int64_t capacity)
+int64_t pisces_hip_format_vcf_padded_ex(const PiscesVcfConfig* cfg, const char* chrom, const PiscesCalledAllele* recs, int64_t n,
+                                        const int32_t* cand_index, const PiscesCandidate* cands, const uint8_t* alleles,
+                                        const uint8_t* ref_bases, int64_t ref_len, const int32_t* interval_starts,
+                                        const int32_t* interval_ends, int32_t n_intervals, PiscesVcfPadState* state, int32_t finish,
+                                        char* out, int64_t capacity, const PiscesGenotypePosteriors* gp)
 {
     try {   // nothing crosses the C ABI as an exception (std::bad_alloc from the text buffer, ...)
     return [&]() -> int64_t {
@@ -325,9 +325,15 @@ int64_t pisces_hip_format_vcf_padded(const PiscesVcfConfig* cfg, const char* chr
             const float nc = all == 0.0f ? 0.0f : (float)first.num_no_calls / all;
             sample += ":" + fmt_single(nc, 4);
         }
+        // ShouldReportGp (VcfFormatter.cs:263-269): the first allele's posteriors, each ToString("0.00")
+        const bool with_gp = gp && gp[g0].n > 0;
+        if (with_gp) {
+            sample += ":";
+            for (int k = 0; k < gp[g0].n && k < 6; k++) sample += (k ? "," : "") + fmt_single(gp[g0].gp[k], 2);
+        }
         text += chrom;
         text += "\t" + std::to_string(first.position) + "\t.\t" + ref_allele + "\t" + ((ref_like_gt && !forced_to_report) ? std::string(".") : alt_allele) + "\t" +
-                std::to_string(qual) + "\t" + filters + "\tDP=" + std::to_string(depth) + "\t" + format + "\t" + sample + "\n";
+                std::to_string(qual) + "\t" + filters + "\tDP=" + std::to_string(depth) + "\t" + format + (with_gp ? ":GP" : "") + "\t" + sample + "\n";
         st.last_variant_position_written = first.position;
         g0 = g1;
     }
@@ -346,6 +352,22 @@ int64_t pisces_hip_format_vcf_padded(const PiscesVcfConfig* cfg, const char* chr
     } catch (...) {
         return PISCES_E_INTERNAL;
     }
+}
+
+int64_t pisces_hip_format_vcf_padded(const PiscesVcfConfig* cfg, const char* chrom, const PiscesCalledAllele* recs, int64_t n,
+                                     const int32_t* cand_index, const PiscesCandidate* cands, const uint8_t* alleles,
+                                     const uint8_t* ref_bases, int64_t ref_len, const int32_t* interval_starts,
+                                     const int32_t* interval_ends, int32_t n_intervals, PiscesVcfPadState* state, int32_t finish,
+                                     char* out, int64_t capacity)
+{
+    return pisces_hip_format_vcf_padded_ex(cfg, chrom, recs, n, cand_index, cands, alleles, ref_bases, ref_len, interval_starts, interval_ends, n_intervals, state,
+                                           finish, out, capacity, nullptr);
+}
+
+int64_t pisces_hip_format_vcf_ex(const PiscesVcfConfig* cfg, const char* chrom, const PiscesCalledAllele* recs, int64_t n, const int32_t* cand_index,
+                                 const PiscesCandidate* cands, const uint8_t* alleles, char* out, int64_t capacity, const PiscesGenotypePosteriors* gp)
+{
+    return pisces_hip_format_vcf_padded_ex(cfg, chrom, recs, n, cand_index, cands, alleles, nullptr, 0, nullptr, nullptr, 0, nullptr, 0, out, capacity, gp);
 }
 
 int64_t pisces_hip_format_vcf(const PiscesVcfConfig* cfg, const char* chrom, const PiscesCalledAllele* recs, int64_t n,

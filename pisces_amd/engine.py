@@ -232,6 +232,36 @@ class HipVariantCaller:
         w.__array_interface__ = {"shape": (n,), "typestr": "|V%d" % _abi.CALLED_ALLELE_DTYPE.itemsize, "data": (rows.value, False), "version": 3}
         return np.asarray(w).view(_abi.CALLED_ALLELE_DTYPE)
 
+    def Posteriors(self, capacity=1 << 16):
+        """CalledAllele.GenotypePosteriors of the rows the last Call* returned (pisces_hip_get_posteriors): a POSTERIORS_DTYPE array, row i
+        of it for row i of the rows; n = 0 where a row has none (every row of a handle that is not PLOIDY_DIPLOID_ADAPTIVE)."""
+        while True:
+            out = np.zeros(capacity, dtype=_abi.POSTERIORS_DTYPE)
+            n = C.c_int64(0)
+            rc = lib.pisces_hip_get_posteriors(self._h, out.ctypes.data, len(out), C.byref(n))
+            if rc == _abi.E_BUFFER_TOO_SMALL:
+                capacity = int(n.value)
+                continue
+            _check(self._h, rc)
+            return out[: n.value]
+
+    def PosteriorsView(self):
+        """pisces_hip_posteriors_view: Posteriors() without the copy, valid as long as the rows of CallView / CallEndView are."""
+        rows, n = C.c_void_p(), C.c_int64(0)
+        _check(self._h, lib.pisces_hip_posteriors_view(self._h, C.byref(rows), C.byref(n)))
+        if not n.value:
+            return np.zeros(0, dtype=_abi.POSTERIORS_DTYPE)
+        w = _RowsAt()
+        w.__array_interface__ = {"shape": (n.value,), "typestr": "|V%d" % _abi.POSTERIORS_DTYPE.itemsize, "data": (rows.value, False), "version": 3}
+        return np.asarray(w).view(_abi.POSTERIORS_DTYPE)
+
+    def SetAdaptiveGenotypingParameters(self, snv_model=None, indel_model=None, snv_prior=None, indel_prior=None, sum_vf_for_multi_allelic_site=None,
+                                        max_genotype_posteriors=None):
+        """AdaptiveGenotypingParameters of a PLOIDY_DIPLOID_ADAPTIVE caller (pisces_hip_set_adaptive_params); what is not given keeps the
+        reference's default."""
+        self._adaptive = adaptive_params(snv_model, indel_model, snv_prior, indel_prior, sum_vf_for_multi_allelic_site, max_genotype_posteriors)
+        _check(self._h, lib.pisces_hip_set_adaptive_params(self._h, C.byref(self._adaptive)))
+
     def CallBegin(self, upToPosition=None):
         """pisces_hip_flush_begin: the flush enqueued, DoneProcessing committed; the alleles come with CallEnd.  In between the next
         reads may be staged and added."""
@@ -456,8 +486,12 @@ class HipVariantCaller:
                              "own stream, after synchronizing your fills) or allocate under caller.torch_stream() and pass that")
         return raw
 
-    def call_tiles(self, d_tuples, d_tiles, n_tiles, d_ref, ref_start, ref_len, d_records, capacity, d_tile_results, stream=None):
-        """All pointer arguments are raw device addresses (ints); capacity >= 256 * n_tiles record slots."""
+    def call_tiles(self, d_tuples, d_tiles, n_tiles, d_ref, ref_start, ref_len, d_records, capacity, d_tile_results, stream=None, posteriors=None):
+        """All pointer arguments are raw device addresses (ints); capacity >= 256 * n_tiles record slots.  posteriors (a
+        PLOIDY_DIPLOID_ADAPTIVE caller): a device tensor of 32 * capacity bytes, slot-parallel to the records, that this and every later
+        launch fills (pisces_hip_set_posteriors_buffer)."""
+        if posteriors is not None:
+            _check(self._h, lib.pisces_hip_set_posteriors_buffer(self._h, posteriors.data_ptr(), posteriors.numel() * posteriors.element_size() // 32))
         _check(self._h, lib.pisces_hip_call_tiles(self._h, d_tuples, d_tiles, n_tiles, d_ref, ref_start, ref_len,
                                                   d_records, capacity, d_tile_results, self._stream_arg(stream)))
 
@@ -491,6 +525,11 @@ class HipVariantCaller:
     def compact_records(self, d_records, d_tile_results, n_tiles, d_offsets, d_out, out_capacity, d_count, stream=None):
         _check(self._h, lib.pisces_hip_compact_records(self._h, d_records, d_tile_results, n_tiles, d_offsets, d_out,
                                                        out_capacity, d_count, self._stream_arg(stream)))
+
+    def compact_posteriors(self, d_posteriors, d_tile_results, n_tiles, d_offsets, d_out, out_capacity, stream=None):
+        """pisces_hip_compact_posteriors: after compact_records, with the d_offsets it filled."""
+        _check(self._h, lib.pisces_hip_compact_posteriors(self._h, d_posteriors, d_tile_results, n_tiles, d_offsets, d_out, out_capacity,
+                                                          self._stream_arg(stream)))
 
     def accumulate_tiles(self, d_tuples, d_tiles, n_tiles, d_counts, stream=None):
         _check(self._h, lib.pisces_hip_accumulate_tiles(self._h, d_tuples, d_tiles, n_tiles, d_counts, self._stream_arg(stream)))
@@ -640,13 +679,62 @@ def expand_reads(batch, min_base_call_quality=20):
         return pos[:n], tup[:n]
 
 
+def adaptive_params(snv_model=None, indel_model=None, snv_prior=None, indel_prior=None, sum_vf_for_multi_allelic_site=None, max_genotype_posteriors=None):
+    """_abi.PiscesAdaptiveParams: the reference's defaults (pisces_hip_adaptive_default_params) with the given members replaced"""
+    p = _abi.PiscesAdaptiveParams()
+    _check(None, lib.pisces_hip_adaptive_default_params(C.byref(p)))
+    for name, v in (("snv_model", snv_model), ("indel_model", indel_model), ("snv_prior", snv_prior), ("indel_prior", indel_prior)):
+        if v is not None:
+            setattr(p, name, (C.c_double * 3)(*[float(x) for x in v]))
+    if sum_vf_for_multi_allelic_site is not None:
+        p.sum_vf_for_multi_allelic_site = float(sum_vf_for_multi_allelic_site)
+    if max_genotype_posteriors is not None:
+        p.max_genotype_posteriors = int(max_genotype_posteriors)
+    return p
+
+
+def set_genotypes_adaptive(alleles, config=None, params=None):
+    """pisces_hip_set_genotypes_adaptive over the alleles of one locus: alleles = list of dicts(category, ref, alt, support, coverage[,
+    reference_support]).  Returns (locus genotype, list of dicts(genotype, genotype_qscore, phase_set_index, multi_allelic, prune), posteriors
+    as a POSTERIORS_DTYPE array)."""
+    cfg = config if config is not None else _abi.default_config()
+    par = params if params is not None else adaptive_params()
+    n = len(alleles)
+    arr = (_abi.PiscesGenotypeAllele * max(n, 1))()
+    pool = bytearray()
+    for i, a in enumerate(alleles):
+        arr[i].category, arr[i].ref_len, arr[i].alt_len = int(a["category"]), len(a["ref"]), len(a["alt"])
+        arr[i].support, arr[i].coverage, arr[i].reference_support = int(a["support"]), int(a["coverage"]), int(a.get("reference_support", 0))
+        arr[i].allele_offset = len(pool)
+        pool += a["ref"].encode() + a["alt"].encode()
+    pool_arr = np.frombuffer(bytes(pool) + b"\0", dtype=np.uint8).copy()
+    post = np.zeros(max(n, 1), dtype=_abi.POSTERIORS_DTYPE)
+    gt = lib.pisces_hip_set_genotypes_adaptive(C.byref(cfg), C.byref(par), arr, n, pool_arr.ctypes.data, len(pool), post.ctypes.data)
+    if gt < 0:
+        raise PiscesHipError(int(gt), "set_genotypes_adaptive failed")
+    res = [dict(genotype=arr[i].genotype, genotype_qscore=arr[i].genotype_qscore, phase_set_index=arr[i].phase_set_index,
+                multi_allelic=bool(arr[i].multi_allelic), prune=bool(arr[i].prune)) for i in range(n)]
+    return int(gt), res, post[:n]
+
+
+def adaptive_genotype_qscore(allele_support, total_coverage, category=_abi.CAT_SNV, is_reference=False, params=None):
+    """pisces_hip_adaptive_genotype_qscore: (mixture component 0 / 1 / 2, q-score 0..100, three phred-scaled posteriors)"""
+    par = params if params is not None else adaptive_params()
+    cat, q = C.c_int32(0), C.c_int32(0)
+    gp = (C.c_float * 3)()
+    _check(None, lib.pisces_hip_adaptive_genotype_qscore(C.byref(par), int(category), int(bool(is_reference)), int(allele_support), int(total_coverage),
+                                                         C.byref(cat), C.byref(q), gp))
+    return cat.value, q.value, np.array(list(gp), dtype=np.float32)
+
+
 def new_pad_state():
     """Cursors of a VCF writer + RegionMapper pair at the start of a chromosome (PiscesVcfPadState)."""
     return _abi.PiscesVcfPadState(0, 0, -1)
 
 
-def format_vcf(chrom, records, vcf_config=None, alleles=None, pad=None, **overrides):
-    """VCF body lines of `records` (pisces_hip_format_vcf[_padded]).  alleles: the (ref, alt) string pairs CallWithAlleles returned, needed
+def format_vcf(chrom, records, vcf_config=None, alleles=None, pad=None, posteriors=None, **overrides):
+    """VCF body lines of `records` (pisces_hip_format_vcf[_padded][_ex]).  posteriors: the POSTERIORS_DTYPE array Posteriors() returned for
+    these rows (the GP column of PloidyModel.DiploidByAdaptiveGT), None = none.  alleles: the (ref, alt) string pairs CallWithAlleles returned, needed
     for insertion / deletion / MNV rows; vcf_config: _abi.PiscesVcfConfig or None for the defaults (+ field overrides, e.g. crush=1).
     pad: dict(state=new_pad_state(), reference=bytes, intervals=[(start, end), ...], finish=bool) adds RegionMapper's no-call rows for
     uncovered interval positions; the state object is advanced in place."""
@@ -658,6 +746,11 @@ def format_vcf(chrom, records, vcf_config=None, alleles=None, pad=None, **overri
         setattr(cfg, k, v)
     recs = np.ascontiguousarray(records)
     n = len(recs)
+    gp = None
+    if posteriors is not None:
+        gp = np.ascontiguousarray(posteriors, dtype=_abi.POSTERIORS_DTYPE)
+        if len(gp) != n:
+            raise ValueError("format_vcf: posteriors must have one entry per record")
     idx = cands = pool_arr = None
     if alleles is not None:
         idx_l, cand_l, pool = [], [], bytearray()
@@ -684,11 +777,11 @@ def format_vcf(chrom, records, vcf_config=None, alleles=None, pad=None, **overri
     cap = 256 * max(n, 1) + 128 * (int((ends - starts + 1).sum()) if pad is not None and n_iv else 0)
     while True:
         buf = C.create_string_buffer(max(cap, 1))
-        need = lib.pisces_hip_format_vcf_padded(
+        need = lib.pisces_hip_format_vcf_padded_ex(
             C.byref(cfg), chrom.encode(), recs.ctypes.data if n else None, n, idx.ctypes.data if idx is not None else None, cands,
             pool_arr.ctypes.data if pool_arr is not None else None, refa.ctypes.data if refa is not None else None,
             refa.size if refa is not None else 0, starts.ctypes.data if n_iv else None, ends.ctypes.data if n_iv else None, n_iv,
-            C.byref(state) if state is not None else None, finish, buf, cap)
+            C.byref(state) if state is not None else None, finish, buf, cap, gp.ctypes.data if gp is not None and n else None)
         if need < 0:
             raise PiscesHipError(int(need), "format_vcf failed")
         if need <= cap:
