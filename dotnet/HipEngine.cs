@@ -34,6 +34,12 @@ namespace Pisces.Hip
         private readonly List<byte> _flags = new List<byte>(), _cigOp = new List<byte>(), _bases = new List<byte>(), _quals = new List<byte>(), _dirs = new List<byte>(), _delDirs = new List<byte>();
         private readonly List<uint> _cigLen = new List<uint>();
         private bool _anyStitched, _anyDelDirs;
+        // -abfilter: the XN names of this chromosome's reads as the int32 ids that cross the boundary (one engine per (BAM, chromosome) job), in
+        // arrival order; _ampId holds the staged reads' ids, -1 for a read without the tag
+        private bool _trackAmplicons;
+        private readonly Dictionary<string, int> _ampliconIds = new Dictionary<string, int>();
+        private readonly List<string> _ampliconNames = new List<string>();
+        private readonly List<int> _ampId = new List<int>();
         // BlocksPerFlush > 1 holds the native flush back until upTo has moved that many blocks on: records come out later, in the same
         // order (the VCF writer does not care), and the per-flush latency (~0.26 ms) is paid once per group (DESIGN.md section 8)
         public int BlocksPerFlush = 1;
@@ -83,6 +89,26 @@ namespace Pisces.Hip
             NativeMethods.Check(IntPtr.Zero, NativeMethods.pisces_hip_create(ref c, device, out _h));
         }
 
+        /// Factory.ShouldTrackAmpliconCounts (AmpliconBiasFilterThreshold.HasValue): before the first read.  The library refuses the
+        /// combinations it does not serve (MNV calling, forced alleles, ...) with PISCES_E_UNSUPPORTED, which Check turns into an exception.
+        public void SetAmpliconBiasFilter(float? threshold)
+        {
+            _trackAmplicons = threshold.HasValue;
+            NativeMethods.Check(_h, NativeMethods.pisces_hip_set_amplicon_bias_filter(_h, threshold ?? -1f));
+        }
+
+        /// IAlleleSource.GetCoverageByAmplicon: the native slots (ascending id) back to names
+        public AmpliconCounts GetCoverageByAmplicon(int position)
+        {
+            var counts = AmpliconCounts.GetEmptyAmpliconCounts();
+            if (!_trackAmplicons) return counts;
+            FlushStagedReads(null);
+            int[] ids = new int[6], coverage = new int[6], support = new int[24];
+            NativeMethods.Check(_h, NativeMethods.pisces_hip_get_amplicon_counts(_h, position, 1, ids, coverage, support));
+            for (int s = 0; s < 6 && ids[s] >= 0; s++) { counts.AmpliconNames[s] = _ampliconNames[ids[s]]; counts.CountsForAmplicon[s] = coverage[s]; }
+            return counts;
+        }
+
         /// PloidyModel.DiploidByAdaptiveGT: VariantCallingParameters.AdaptiveGenotypingParameters to the handle (the defaults are the library's too)
         public unsafe void SetAdaptiveGenotypingParameters(AdaptiveGenotypingParameters a)
         {
@@ -129,6 +155,13 @@ namespace Pisces.Hip
             var map = read.SequencedBaseDirectionMap;                               // per-base DirectionType (stitched reads: XD tag)
             for (int i = 0; i < map.Length; i++) { _dirs.Add((byte)map[i]); _anyStitched |= map[i] == DirectionType.Stitched; }
             _seqOff.Add(_bases.Count);
+            if (_trackAmplicons)
+            {
+                var name = read.GetAmpliconNameIfExists();
+                int id = -1;
+                if (name != null && !_ampliconIds.TryGetValue(name, out id)) { id = _ampliconNames.Count; _ampliconIds[name] = id; _ampliconNames.Add(name); }
+                _ampId.Add(id);
+            }
         }
 
         /// IStateManager.AddCandidates: the library finds the candidates of the reads itself (NoCandidates is the managed finder), so what
@@ -195,7 +228,9 @@ namespace Pisces.Hip
             for (int i = 0; i < _bases.Count; i++) { v.Bases[i] = _bases[i]; v.Quals[i] = _quals[i]; }
             if (_anyStitched) for (int i = 0; i < _dirs.Count; i++) v.Directions[i] = _dirs[i];
             if (_anyDelDirs) for (int i = 0; i < _delDirs.Count; i++) v.DeletionDirections[i] = _delDirs[i];
-            NativeMethods.Check(_h, NativeMethods.pisces_hip_add_reads(_h, ref v));
+            if (_trackAmplicons) NativeMethods.Check(_h, NativeMethods.pisces_hip_add_reads_amplicons(_h, ref v, _ampId.ToArray()));
+            else NativeMethods.Check(_h, NativeMethods.pisces_hip_add_reads(_h, ref v));
+            _ampId.Clear();
             _pos.Clear(); _flags.Clear(); _cigOp.Clear(); _cigLen.Clear(); _bases.Clear(); _quals.Clear(); _dirs.Clear(); _delDirs.Clear(); _anyDelDirs = false;
             _cigOff.Clear(); _cigOff.Add(0); _seqOff.Clear(); _seqOff.Add(0); _anyStitched = false;
         }

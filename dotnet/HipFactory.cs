@@ -65,6 +65,7 @@ namespace Pisces.Hip
             if (intervalSet != null) _engine.SetIntervals(intervalSet);
             _engine.SetAdaptiveGenotypingParameters(_options.VariantCallingParameters.AdaptiveGenotypingParameters);   // (DiploidByAdaptiveGT only)
             _engine.SetForcedAlleles(_forcedGtAlleles);   // -forcedalleles: ForcedReport rows, reference rows at forced positions
+            _engine.SetAmpliconBiasFilter(_options.VariantCallingParameters.AmpliconBiasFilterThreshold);   // Factory.ShouldTrackAmpliconCounts (null: off)
             return new HipStateManager(_engine);
         }
 
@@ -161,11 +162,12 @@ namespace Pisces.Hip
         // (CollapedRegionStateManager.cs:33); RegionStateManager itself returns 0 (RegionStateManager.cs: the virtual no-op
         // AddCollapsedReadCount), and so does this state manager: Factory.CreateStateManager is asked for the plain one here.
         public int GetCollapsedReadCount(int position, Pisces.Domain.Types.ReadCollapsedType type) { return 0; }
-        // Consumers: ExactCoverageCalculator (only with the exact-coverage option, which HipAlleleCaller does not run) and the amplicon-bias
-        // calculator (off by default; AmpliconBiasFilterThreshold null).  The native path carries neither, as RegionStateManager
-        // carries none without an amplicon-tagged BAM.
+        // Consumer: ExactCoverageCalculator (only with the exact-coverage option, which HipAlleleCaller does not run): not carried.
         public List<ReadCoverageSummary> GetSpanningReadSummaries(int startPosition, int endPosition) { return new List<ReadCoverageSummary>(); }
-        public AmpliconCounts GetCoverageByAmplicon(int position) { return AmpliconCounts.GetEmptyAmpliconCounts(); }
+        // The amplicon-bias calculator's coverage (-abfilter): the native per-amplicon counts of the read store, the XN names restored from
+        // the engine's per-chromosome dictionary; empty when the filter is off, as RegionStateManager's is without tracking.  The filter
+        // itself is applied by the native flush (FilterType.AmpliconBias arrives in the row's filter bits).
+        public AmpliconCounts GetCoverageByAmplicon(int position) { return _e.GetCoverageByAmplicon(position); }
         public bool ExpectStitchedReads { get { return _e.ExpectStitchedReads; } }
     }
 

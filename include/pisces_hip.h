@@ -668,6 +668,54 @@ int32_t pisces_hip_adaptive_genotype_qscore(const PiscesAdaptiveParams* params, 
                                             int32_t total_coverage, int32_t* category_out, int32_t* qscore_out, float* gp_out);
 /* DiploidGenotypeQualityCalculator.Compute (Thresholding/DiploidGenotypeQualityCalculator.cs:17-103) for one allele */
 int32_t pisces_hip_diploid_genotype_qscore(int32_t genotype, int32_t total_coverage, int32_t allele_support, int32_t min_qscore, int32_t max_qscore);
+/* AmpliconBiasCalculator.CalculateAmpliconBias (src/lib/Pisces.Calculators/AmpliconBiasCalculator.cs:45-134; -abfilter, FILTER AB) for ONE
+ * SNV, host only, no handle: entry i of the two arrays is one amplicon of the locus' CoverageByAmplicon, support[i] what the allele's
+ * SupportByAmplicon holds under the same name (0 when it holds none, AmpliconCounts.GetCountsForAmplicon); counts >= 0, any order (no
+ * decision depends on it).  With freq_i = support_i / coverage_i (0 without coverage) and expected_i = max(freq) * coverage_i, an
+ * amplicon's chance is 1 when expected_i < 5, expected_i <= support_i or freq_i > 0.1, else max(0, Poisson.Cdf(support_i, expected_i))
+ * (Pisces' own stats/Poisson.cs).  Returns 1 when any chance < (double)threshold (the row gets PISCES_FILTER_AMPLICON_BIAS), 0 when none is,
+ * and -1 for no result (AmpliconBiasResults stays null, nothing to filter on): n < 2, or no entry of `support` above zero — aligned by
+ * name, a support list without counts and an empty one are the same arrays; the reference fails neither.  -1 as well for a NULL array: this
+ * entry returns no PISCES_E_* code.  chance_out[n] (may be NULL) receives the chances when the result is 0 or 1.  The per-amplicon
+ * q-score and AmpliconWithCandidateArtifact (the AmpliconBias.csv columns) are not computed.  csrc/amplicon_bias.h, written for host and
+ * device alike. */
+int32_t pisces_hip_amplicon_bias(const int32_t* support, const int32_t* coverage, int32_t n, float threshold, double* chance_out);
+
+/* ---- the amplicon-bias filter on the streaming surface (VariantCallingParameters.AmpliconBiasFilterThreshold, -abfilter, FILTER AB) ----
+ * Factory.ShouldTrackAmpliconCounts: threshold >= 0 makes the handle track per-amplicon counts and end every flush (pisces_hip_flush, _ex,
+ * _view, _begin / _end*) with the filter: for every called SNV row with support, CoverageByAmplicon of its position and the row's
+ * SupportByAmplicon go through the decision of pisces_hip_amplicon_bias, and a detected bias ORs 1 << PISCES_FILTER_AMPLICON_BIAS into the row's
+ * filter_bits (AlleleProcessor.ApplyFilters, AlleleProcessor.cs:45-63) — nothing else of the row changes, rows of other categories never get
+ * it (AmpliconBiasCalculator.cs:27).  threshold < 0 = null: off, the default; a handle that is off launches nothing for it.  Must come before
+ * the first read is added (PISCES_E_STATE afterwards).  A read's amplicon (Read.GetAmpliconNameIfExists: the BAM XN tag, Read.cs:483-486)
+ * crosses as an int32 id the host chooses, -1 = no tag.  PISCES_E_UNSUPPORTED, each with a message, for what cannot go together with
+ * tracking: call_mnvs, collapse thresholds that take SNV candidates from the read walk (collapse_freq_threshold > 0 or
+ * collapse_freq_ratio_threshold >= 1), forced alleles (set before: the setter refuses; pisces_hip_set_forced_alleles refuses afterwards),
+ * PISCES_HIP_READ_PATH=log; and on a tracking handle pisces_hip_add_decoded_reads (the XN tag is not decoded on the device yet) and
+ * pisces_hip_add_observations (tuples have no read identity).  The tuple surface (pisces_hip_call_tiles*) never had tags and is untouched.
+ * A flush that meets a position with more than six amplicons (Constants.MaxNumOverlappingAmplicons, Constants.cs:54-62: the reference
+ * indexes slot -1 and throws IndexOutOfRangeException) returns PISCES_E_INVALID_ARG naming the lowest such position; the blocks stay held.
+ * A flush counts only in the 64-locus tiles that hold a called SNV row with support (the others cannot get the filter and are skipped), so
+ * it meets such a position only there; pisces_hip_get_amplicon_counts counts every tile of its range and always reports it.
+ * min_base_call_quality above 127 is served: the store's per-base codes hold the quality test only up to 127, above it the counting reads
+ * the qualities themselves, so the counts by amplicon drop the bases the caller's own counts drop.
+ * A tracking flush waits for its kernels before it returns (pisces_hip_flush_begin included). */
+int32_t pisces_hip_set_amplicon_bias_filter(PiscesHip* h, float threshold);
+/* pisces_hip_add_reads / pisces_hip_add_device_reads with one id per read (amplicon_id[n_reads]; the device form's is a device pointer,
+ * copied like the batch).  pisces_hip_stage_reads' views are accepted by the host form.  On a handle without the filter the ids are ignored
+ * and nothing is stored: exactly the plain add.  On a tracking handle the plain adds still work, their reads carry -1 (they count in no
+ * slot).  An id below -1: PISCES_E_INVALID_ARG, the state unchanged. */
+int32_t pisces_hip_add_reads_amplicons(PiscesHip* h, const PiscesReadBatch* batch, const int32_t* amplicon_id);
+int32_t pisces_hip_add_device_reads_amplicons(PiscesHip* h, const PiscesReadBatch* device_batch, int64_t n_cigar_ops, int64_t n_bases,
+                                              const int32_t* device_amplicon_id);
+/* IAlleleSource.GetCoverageByAmplicon for [start_position, start_position + n) plus the support split, same rules as pisces_hip_get_counts
+ * (positions of held blocks; others read as empty): ids[n][6] the amplicon ids of a position, coverage[n][6] their counts of A/C/G/T bases
+ * at or above the minimum base quality (deleted positions, N and low-quality bases and reads without a tag count nowhere,
+ * RegionStateManager.cs:179-189), support[n][4][6] the same split by base in the order A C G T (an SNV's SupportByAmplicon is the row of
+ * its alternate base).  Slots are in ASCENDING ID order with -1 / 0 in the unused ones: the reference's first-arrival order is not
+ * reproduced, and no decision depends on it.  PISCES_E_STATE on a handle that does not track; more than six ids at a position of the range:
+ * PISCES_E_INVALID_ARG as in a flush. */
+int32_t pisces_hip_get_amplicon_counts(PiscesHip* h, int32_t start_position, int32_t n, int32_t* ids, int32_t* coverage, int32_t* support);
 
 /* ---- VCF body lines (pure CPU) ---------------------------------------
  * What the writer needs of VcfWriterConfig (src/lib/Pisces.IO/VcfFileWriter.cs:264-330). */

@@ -25,6 +25,8 @@ EXPORTS = [
     "pisces_hip_add_device_reads", "pisces_hip_get_stream", "pisces_hip_comm_library", "pisces_hip_comm_ranks", "pisces_hip_set_known_variants", "pisces_hip_set_exclude_mnvs_from_collapsing", "pisces_hip_set_exact_total_called", "pisces_hip_reallocate_failed_mnvs", "pisces_hip_set_genotypes", "pisces_hip_diploid_genotype_qscore",
     "pisces_hip_adaptive_default_params", "pisces_hip_set_adaptive_params", "pisces_hip_get_posteriors", "pisces_hip_posteriors_view", "pisces_hip_set_posteriors_buffer",
     "pisces_hip_compact_posteriors", "pisces_hip_set_genotypes_adaptive", "pisces_hip_adaptive_genotype_qscore", "pisces_hip_format_vcf_ex", "pisces_hip_format_vcf_padded_ex",
+    "pisces_hip_amplicon_bias", "pisces_hip_set_amplicon_bias_filter", "pisces_hip_add_reads_amplicons", "pisces_hip_add_device_reads_amplicons",
+    "pisces_hip_get_amplicon_counts",
 ]
 
 
@@ -80,6 +82,11 @@ def _load():
         "pisces_hip_compact_posteriors": (i32, [vp, vp, vp, i32, vp, vp, i32, vp]),
         "pisces_hip_set_genotypes_adaptive": (i32, [P(_abi.PiscesHipConfig), P(_abi.PiscesAdaptiveParams), P(_abi.PiscesGenotypeAllele), i32, vp, i64, vp]),
         "pisces_hip_adaptive_genotype_qscore": (i32, [P(_abi.PiscesAdaptiveParams), i32, i32, i32, i32, P(i32), P(i32), P(C.c_float)]),
+        "pisces_hip_amplicon_bias": (i32, [P(i32), P(i32), i32, C.c_float, P(C.c_double)]),
+        "pisces_hip_set_amplicon_bias_filter": (i32, [vp, C.c_float]),
+        "pisces_hip_add_reads_amplicons": (i32, [vp, P(_abi.PiscesReadBatch), vp]),
+        "pisces_hip_add_device_reads_amplicons": (i32, [vp, P(_abi.PiscesReadBatch), i64, i64, vp]),
+        "pisces_hip_get_amplicon_counts": (i32, [vp, i32, i32, vp, vp, vp]),
         "pisces_hip_stage_reads": (i32, [vp, i32, i64, i64, i32, i32, P(_abi.PiscesReadBatch)]),
         "pisces_hip_flush_begin": (i32, [vp, i32]),
         "pisces_hip_flush_end": (i32, [vp, vp, i64, P(i64)]),

@@ -35,6 +35,7 @@
 #include "kernels.hip.h"
 #include "stream_kernels.hip.h"
 #include "store_kernels.hip.h"
+#include "amplicon_kernels.hip.h"
 #include "finder_kernels.hip.h"
 #include "bgzf_kernels.hip.h"
 #include "bam_kernels.hip.h"
@@ -260,6 +261,7 @@ struct ReadSegment {
     DeviceBuf<ReadDesc> desc;
     DeviceBuf<ReadExt> ext;
     DeviceBuf<ReadDesc> frag;    // one per CIGAR operation: what the flush kernel walks
+    DeviceBuf<int32_t> amp_read_ids, amp_frag_ids;   // a tracking handle (pisces_hip_set_amplicon_bias_filter): the amplicon id of every read / fragment
     DeviceBuf<int32_t> grid;     // the position grid (store_kernels.hip.h grid_cells): first fragment per position (cell) from cell grid_base on
     int64_t grid_base = 0, grid_n = 0;
     bool grid_ok = false;        // every batch so far could extend it (known first position, not before grid_base, a sane span)
@@ -305,6 +307,11 @@ struct PiscesHip {
     // loci OUTSIDE the intervals too (AlleleCaller.cs:109-131: IsCallable counts, ShouldReport comes after): a second launch of the flush
     // kernel over those loci of the flushed blocks, its records dropped, its n_called added
     bool exact_total_called = false;
+    // pisces_hip_set_amplicon_bias_filter: per-amplicon counts are tracked and every flush ends with amplicon_tiles_kernel
+    bool amp_on = false;
+    float amp_threshold = -1.0f;
+    const int32_t* amp_pending = nullptr;   // the ids (in d_amp_in) of the batch an *_amplicons add is handing to the plain add; nullptr: -1 throughout
+    DeviceBuf<int32_t> d_amp_in, d_amp_words, d_amp_table;
     DeviceBuf<PiscesTile> d_tiles_x;
     DeviceBuf<PiscesTileResult> d_tr_x;
     DeviceBuf<PiscesCalledAllele> d_rec_x;
@@ -1184,6 +1191,8 @@ int32_t pisces_hip_set_owned_range(PiscesHip* h, int32_t lo, int32_t hi)
 #include "surface_bam.inc.h"
 
 #include "surface_comm.inc.h"
+
+#include "surface_amplicon.inc.h"
 
 int32_t pisces_hip_synchronize(PiscesHip* h)
 {

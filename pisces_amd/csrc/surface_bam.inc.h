@@ -351,6 +351,7 @@ int32_t pisces_hip_add_decoded_reads(PiscesHip* h)
 {
     return abi_guard<int32_t>(h, [&]() -> int32_t {
     if (!h) return PISCES_E_INVALID_ARG;
+    if (h->amp_on) return fail(h, PISCES_E_UNSUPPORTED, "add_decoded_reads: the handle tracks amplicon counts (pisces_hip_set_amplicon_bias_filter): the XN tag is not decoded on the device yet");
     if (!h->bam.valid) return fail(h, PISCES_E_STATE, "add_decoded_reads: no decoded batch (pisces_hip_bam_decode first)");
     HostTimer timer(&h->host_time[0]);
     auto& B = h->bam;

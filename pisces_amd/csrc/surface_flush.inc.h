@@ -446,6 +446,12 @@ static int32_t call_blocks_enqueue(PiscesHip* h, const std::vector<int32_t>& key
         PISCES_HIP_CHECK(h, h->d_post.reserve(cap));
         PISCES_HIP_CHECK(h, h->d_post_compact.reserve(cap));
     }
+    // pisces_hip_set_amplicon_bias_filter: FilterType.AmpliconBias joins the slot records behind whichever tile kernel wrote them and before
+    // the genotyper, the compaction and DoneProcessing (AlleleProcessor.ApplyFilters adds it with the allele's other filters)
+    if (h->amp_on && store) {
+        int32_t rca = amplicon_launch(h, "flush", regular ? (const PiscesTile*)nullptr : (const PiscesTile*)h->d_tiles.p, R, n_tiles, h->d_records.p, h->d_tile_results.p, nullptr);
+        if (rca) return rca;
+    }
     if (genotype_on_device) launch_genotype_loci(h, h->stream, h->d_records.p, h->d_tile_results.p, n_tiles, with_posteriors ? h->d_post.p : nullptr);
     // tiles were built in ascending position order: the ordered compaction is AlleleCaller.Call's (position, ref, alt) order.
     // The sorted records lie behind one header slot {records, called}.  A launch of up to 64 tiles (the blocks of one flush of the

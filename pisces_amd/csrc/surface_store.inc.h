@@ -603,6 +603,52 @@ static int32_t store_device_checks(PiscesHip* h, uint8_t* d, const StageLayout& 
     return PISCES_OK;
 }
 
+// A tracking handle (pisces_hip_set_amplicon_bias_filter): the ids of the batch that is about to join segment g, behind the ids the
+// segment holds — whichever way the batch was placed (a segment of its own: from slot 0; appended: behind n_reads / n_ops).  They survive
+// floors with the descriptors and go with the segment's other buffers.
+static int32_t amplicon_store_ids(PiscesHip* h, ReadSegment& g, const int32_t* d_cigar_offset, int32_t nr, size_t n_cig)
+{
+    const size_t n0 = (size_t)g.n_reads, o0 = (size_t)g.n_ops;
+    PISCES_HIP_CHECK(h, g.amp_read_ids.grow_keep(n0 + (size_t)nr, n0, h->stream));
+    PISCES_HIP_CHECK(h, g.amp_frag_ids.grow_keep(o0 + n_cig + 1, o0, h->stream));
+    hipLaunchKernelGGL(amplicon_scatter_ids_kernel, dim3((unsigned)((nr + 255) / 256)), dim3(256), 0, h->stream, h->amp_pending, d_cigar_offset, nr, (int32_t)n_cig,
+                       g.amp_read_ids.p + n0, g.amp_frag_ids.p + o0);
+    PISCES_HIP_CHECK(h, hipGetLastError());
+    return PISCES_OK;
+}
+static void amplicon_view(PiscesHip* h, AmpliconView* A)
+{
+    std::memset(A, 0, sizeof(*A));
+    int n = 0;
+    for (auto& sp : h->segments) {   // (store_view's order and its skips)
+        if (sp->n_reads == 0 || n == kMaxSegments) continue;
+        A->read_ids[n] = sp->amp_read_ids.p;
+        A->frag_ids[n] = sp->amp_frag_ids.p;
+        n++;
+    }
+}
+// amplicon_tiles_kernel over n_tiles tiles (d_tiles, or R when nullptr).  records: the flush's pass over the slot records; table: the tiles'
+// tables for pisces_hip_get_amplicon_counts.  Waits for the launch: a position with more than six amplicons is an error of the call.
+static int32_t amplicon_launch(PiscesHip* h, const char* what, const PiscesTile* d_tiles, const RegularTiles& R, int32_t n_tiles, PiscesCalledAllele* d_records,
+                               const PiscesTileResult* d_tr, int32_t* d_table)
+{
+    StoreView V;
+    store_view(h, &V);
+    AmpliconView A;
+    amplicon_view(h, &A);
+    PISCES_HIP_CHECK(h, h->d_amp_words.reserve(4));
+    PISCES_HIP_CHECK(h, hipMemsetD32Async((hipDeviceptr_t)h->d_amp_words.p, kAmpNoOverflow, 1, h->stream));
+    hipLaunchKernelGGL(amplicon_tiles_kernel, dim3((unsigned)n_tiles), dim3(64), 0, h->stream, V, A, d_tiles, R, n_tiles, h->cfg.min_base_call_quality, d_records, d_tr,
+                       h->amp_threshold, h->d_amp_words.p, d_table);
+    PISCES_HIP_CHECK(h, hipGetLastError());
+    int32_t overflow = kAmpNoOverflow;
+    PISCES_HIP_CHECK(h, hipMemcpyAsync(&overflow, h->d_amp_words.p, sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    PISCES_HIP_CHECK(h, hipStreamSynchronize(h->stream));
+    if (overflow != kAmpNoOverflow)
+        return fail(h, PISCES_E_INVALID_ARG, std::string(what) + ": more than 6 amplicons at one position; the reference throws here (position " + std::to_string(overflow) + ")");
+    return PISCES_OK;
+}
+
 // The tail of every add into the read store, once the batch's arrays lie on the device at d and its checks are in (rc_in: their verdict):
 // descriptors and fragments (read_shape_kernel), candidate discovery, and — only now — the handle's state.  fslots_host: the candidate-record
 // slots the host pass made (uploaded here), or nullptr when they were made on the device.
@@ -639,6 +685,7 @@ static int32_t store_finish_add(PiscesHip* h, StorePlace& pl, int32_t rc, uint8_
             rc = enqueue_candidate_discovery(h, db, has_deldirs ? d + L.off_deldirs : nullptr, nr, (const int32_t*)(d + L.off_fslots), found_slots, found_pool);
         h->found.min_position = min_position;   // (a flush up to a position below every read of this batch need not wait for its candidates)
     }
+    if (rc == PISCES_OK && h->amp_on) rc = amplicon_store_ids(h, *pl.seg, db.cigar_offset, nr, n_cig);
     { int32_t rcs = stage_release(h); if (rc == PISCES_OK) rc = rcs; }   // (transfers out of the pinned buffer may be in flight whatever happened after them)
     if (rc) {
         (void)store_run_deferred(h);   // (before the segment's buffers can go)

@@ -255,10 +255,11 @@ int64_t pisces_hip_format_vcf_padded_ex(const PiscesVcfConfig* cfg, const char* 
         std::string filters;
         uint32_t seen = 0;
         // (MultiAllelicSite is added by the diploid genotyper, GenotypeCalculatorUtilities.cs:139-145, after the processor's filters
-        // and before AlleleCaller's LowGQ; ForcedReport by AlleleCaller.cs:112-116, after the processor's filters and before the genotyper)
-        static const int kOrder[9] = {PISCES_FILTER_LOW_DEPTH, PISCES_FILTER_LOW_VARIANT_QSCORE, PISCES_FILTER_NO_CALL, PISCES_FILTER_STRAND_BIAS,
-                                      PISCES_FILTER_RMXN, PISCES_FILTER_LOW_VARIANT_FREQUENCY, PISCES_FILTER_FORCED_REPORT,
-                                      PISCES_FILTER_MULTI_ALLELIC_SITE, PISCES_FILTER_LOW_GENOTYPE_QUALITY};
+        // and before AlleleCaller's LowGQ; ForcedReport by AlleleCaller.cs:112-116, after the processor's filters and before the genotyper;
+        // AmpliconBias sits behind StrandBias and before the repeat filters, AlleleProcessor.cs:45-63, and prints as AB, VcfFormatter.cs:155-156)
+        static const int kOrder[10] = {PISCES_FILTER_LOW_DEPTH, PISCES_FILTER_LOW_VARIANT_QSCORE, PISCES_FILTER_NO_CALL, PISCES_FILTER_STRAND_BIAS,
+                                       PISCES_FILTER_AMPLICON_BIAS, PISCES_FILTER_RMXN, PISCES_FILTER_LOW_VARIANT_FREQUENCY, PISCES_FILTER_FORCED_REPORT,
+                                       PISCES_FILTER_MULTI_ALLELIC_SITE, PISCES_FILTER_LOW_GENOTYPE_QUALITY};
         for (int64_t i = g0; i < g1; i++)
             for (int f : kOrder) {
                 if (!(recs[i].filter_bits & (1u << f)) || (seen & (1u << f))) continue;
@@ -272,6 +273,7 @@ int64_t pisces_hip_format_vcf_padded_ex(const PiscesVcfConfig* cfg, const char* 
                     break;
                 case PISCES_FILTER_NO_CALL: name = "NC"; break;
                 case PISCES_FILTER_STRAND_BIAS: name = "SB"; break;
+                case PISCES_FILTER_AMPLICON_BIAS: name = "AB"; break;
                 case PISCES_FILTER_RMXN:
                     if (cfg->rmxn_max_repeat_length < 0 || cfg->rmxn_min_repetitions < 0) return PISCES_E_INVALID_ARG;
                     name = "R" + std::to_string(cfg->rmxn_max_repeat_length) + "x" + std::to_string(cfg->rmxn_min_repetitions);
@@ -279,7 +281,8 @@ int64_t pisces_hip_format_vcf_padded_ex(const PiscesVcfConfig* cfg, const char* 
                 case PISCES_FILTER_LOW_VARIANT_FREQUENCY: name = "LowVariantFreq"; break;
                 case PISCES_FILTER_FORCED_REPORT: name = "ForcedReport"; break;
                 case PISCES_FILTER_MULTI_ALLELIC_SITE: name = "MultiAllelicSite"; break;
-                default: name = "LowGQ"; break;
+                case PISCES_FILTER_LOW_GENOTYPE_QUALITY: name = "LowGQ"; break;
+                default: return PISCES_E_INTERNAL;   // a bit of kOrder without a name
                 }
                 if (!filters.empty()) filters += ";";
                 filters += name;

@@ -115,17 +115,45 @@ class HipVariantCaller:
         _check(self._h, lib.pisces_hip_set_owned_range(self._h, int(lo), int(hi)))
 
     # ---- IStateManager ----
-    def AddAlleleCounts(self, reads):
-        """IStateManager.AddAlleleCounts for a batch (one _abi.ReadBatch, or an iterable of read dicts)."""
-        batch = reads if isinstance(reads, _abi.ReadBatch) else _abi.ReadBatch(reads)
-        _check(self._h, lib.pisces_hip_add_reads(self._h, C.byref(batch.c)))
+    def SetAmpliconBiasFilter(self, threshold):
+        """VariantCallingParameters.AmpliconBiasFilterThreshold (None = off): before the first read is added."""
+        _check(self._h, lib.pisces_hip_set_amplicon_bias_filter(self._h, -1.0 if threshold is None else float(threshold)))
 
-    def AddDeviceReads(self, reads):
+    def AddAlleleCounts(self, reads, amplicon_ids=None):
+        """IStateManager.AddAlleleCounts for a batch (one _abi.ReadBatch, or an iterable of read dicts); amplicon_ids: one int32 per read
+        (Read.GetAmpliconNameIfExists as an id of the host's choosing, -1 = no tag)."""
+        batch = reads if isinstance(reads, _abi.ReadBatch) else _abi.ReadBatch(reads)
+        if amplicon_ids is None:
+            _check(self._h, lib.pisces_hip_add_reads(self._h, C.byref(batch.c)))
+            return
+        ids = np.ascontiguousarray(amplicon_ids, dtype=np.int32)
+        if ids.shape != (batch.c.n_reads,):
+            raise PiscesHipError(_abi.E_INVALID_ARG, "AddAlleleCounts: one amplicon id per read")
+        _check(self._h, lib.pisces_hip_add_reads_amplicons(self._h, C.byref(batch.c), ids.ctypes.data))
+
+    def GetCoverageByAmplicon(self, position, n=1):
+        """IAlleleSource.GetCoverageByAmplicon for n positions from `position` on: (ids[n][6], coverage[n][6], support[n][4][6] by base A C G T),
+        slots in ascending id order, -1 / 0 in the unused ones."""
+        ids = np.full((n, 6), -1, dtype=np.int32)
+        cov = np.zeros((n, 6), dtype=np.int32)
+        sup = np.zeros((n, 4, 6), dtype=np.int32)
+        _check(self._h, lib.pisces_hip_get_amplicon_counts(self._h, int(position), int(n), ids.ctypes.data, cov.ctypes.data, sup.ctypes.data))
+        return ids, cov, sup
+
+    def AddDeviceReads(self, reads, amplicon_ids=None):
         """pisces_hip_add_device_reads: IStateManager.AddAlleleCounts for a batch that lies in device memory.  `reads`: a DeviceReadBatch
         (torch tensors on the handle's device), or an _abi.ReadBatch whose arrays are copied there first (test plumbing)."""
         b = reads if isinstance(reads, DeviceReadBatch) else DeviceReadBatch.from_host(reads if isinstance(reads, _abi.ReadBatch) else _abi.ReadBatch(reads),
                                                                                        f"cuda:{self.device}")
         b.synchronize()
+        if amplicon_ids is not None:
+            import torch
+            ids = amplicon_ids if isinstance(amplicon_ids, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(amplicon_ids, dtype=np.int32), device=f"cuda:{self.device}")
+            if ids.dtype != torch.int32 or ids.numel() != b.c.n_reads or not ids.is_cuda:
+                raise PiscesHipError(_abi.E_INVALID_ARG, "AddDeviceReads: one int32 amplicon id per read, on the device")
+            torch.cuda.synchronize(ids.device)
+            _check(self._h, lib.pisces_hip_add_device_reads_amplicons(self._h, C.byref(b.c), b.n_ops, b.n_bases, ids.data_ptr()))
+            return
         _check(self._h, lib.pisces_hip_add_device_reads(self._h, C.byref(b.c), b.n_ops, b.n_bases))
 
     def StageReads(self, reads):
@@ -725,6 +753,19 @@ def adaptive_genotype_qscore(allele_support, total_coverage, category=_abi.CAT_S
     _check(None, lib.pisces_hip_adaptive_genotype_qscore(C.byref(par), int(category), int(bool(is_reference)), int(allele_support), int(total_coverage),
                                                          C.byref(cat), C.byref(q), gp))
     return cat.value, q.value, np.array(list(gp), dtype=np.float32)
+
+
+def amplicon_bias(support, coverage, threshold):
+    """pisces_hip_amplicon_bias for the amplicons of one SNV: (True / False / None for "no result", the chance of every amplicon or None)"""
+    sup = np.ascontiguousarray(support, dtype=np.int32)
+    cov = np.ascontiguousarray(coverage, dtype=np.int32)
+    if sup.shape != cov.shape or sup.ndim != 1:
+        raise PiscesHipError(_abi.E_INVALID_ARG, "amplicon_bias: support and coverage are two lists of one length")
+    chance = np.zeros(len(sup), dtype=np.float64)
+    i32p = C.POINTER(C.c_int32)
+    rc = lib.pisces_hip_amplicon_bias(sup.ctypes.data_as(i32p), cov.ctypes.data_as(i32p), len(sup), float(threshold),
+                                      chance.ctypes.data_as(C.POINTER(C.c_double)))
+    return (None, None) if rc < 0 else (bool(rc), chance)
 
 
 def new_pad_state():
