@@ -111,5 +111,208 @@ def filter_scenario():
     return ref, [reads[k] for k in order], [ids[k] for k in order]
 
 
+# the haploid genotyper reports a variant only as the locus' one allele (above 70 %, the reference below 20 %): position -> expected decision
+HAPLOID_PLANTED = {120: True, 140: False, 160: False}
+
+
+def haploid_scenario():
+    """Amplicon A at 300x and amplicon B at 40x over 100..199: 120 every read of A and none of B, 140 every read of both,
+    160 290 reads of A and 38 of B (both above the 10 % that pass freely).  -> (ref, reads, ids), in position order."""
+    ref = reference()
+    alt = lambda p: OTHER[chr(ref[p - 1])]
+    reads, ids = [], []
+    for amp, depth, carriers_160 in ((AMP_A, 300, 290), (AMP_B, 40, 38)):
+        for i in range(depth):
+            edits = {140: alt(140)}
+            if amp == AMP_A:
+                edits[120] = alt(120)
+            if i < carriers_160:
+                edits[160] = alt(160)
+            reads.append(_read(ref, 100, [("M", 100)], reverse=bool(i & 1), edits=edits))
+            ids.append(amp)
+    return ref, reads, ids
+
+
 def names_of(ids):
     return [None if i < 0 else i for i in ids]
+
+
+# ---- seeded generators (the fuzz of tests/test_amplicon_gpu.py; their promises are asserted from the data in tests/test_amplicon_cpu.py) ----
+
+TAGGED_SEEDS = [101, 202]
+WINDOW = 200                       # above the longest reference span random_reads can make (189: six operations of 29, M5, two deletions of 5)
+IDS_A_WINDOW = (3, 2, 1, 2, 1, 3)  # by window % 6: the windows 4..8 of 940..1639 hold 1, 3, 3, 2, 1 ids, so neighbours add up to 4, 6, 5, 3
+ID_POOL = (0, 7, 12, 0x7FFFFFFF, 65535, 1 << 30, 65536, 0x7FFFFFFE, 1, 100003, 255, 31)   # twelve distinct: two neighbouring windows never share an id
+FUZZ_LO, FUZZ_HI = 940, 1640
+FUZZ_REF_LENGTH = 68000
+
+
+def window_ids(position):
+    """The ids a read that starts at `position` may carry: a position sees reads of its own window and of the one before, six ids at the most"""
+    w = position // WINDOW
+    return [ID_POOL[(3 * w + i) % len(ID_POOL)] for i in range(IDS_A_WINDOW[w % 6])]
+
+
+def ref_span(read):
+    return sum(n for op, n in read["cigar"] if op in "M=XDN")
+
+
+def _random_bases(rng, cigar):
+    n = sum(length for op, length in cigar if op in "MIS=X")
+    return (bytes(rng.choice(list(b"ACGTN"), n, p=[.24, .24, .24, .24, .04]).astype(np.uint8)),
+            rng.choice([10, 25, 37, 200], n, p=[.15, .2, .63, .02]).astype(np.uint8).tolist())
+
+
+def _extra_read(rng, pos, cigar):
+    seq, quals = _random_bases(rng, cigar)
+    return {"pos": int(pos), "cigar": list(cigar), "seq": seq, "quals": quals, "reverse": bool(rng.integers(0, 2))}
+
+
+def random_tagged_reads(seed, n=600, lo=FUZZ_LO, hi=FUZZ_HI, exotic=False, tag_all=False, ref_length=FUZZ_REF_LENGTH, extras=True):
+    """tests.test_read_store.random_reads over [lo, hi) with an id per read: one read in seven without a tag (none with tag_all), the others
+    one of window_ids(read position), so that no position ever sees a seventh id.  extras: six reads whose span exceeds 0xFFFF through one
+    long N (one of them ends on the reference's last base), four reads that start at position 1, four that end on the last base.
+    -> (reads, ids) in the order drawn (the callers sort or do not)."""
+    from tests.test_read_store import random_reads
+    rng = np.random.default_rng(seed)
+    reads = random_reads(rng, n, lo, hi, exotic=exotic, sort=False)
+    if extras:
+        for i in range(6):
+            pos = int(rng.integers(1010, 1190))          # one window: at most three ids travel to the far end
+            a, b = int(rng.integers(5, 40)), int(rng.integers(5, 40))
+            gap = 66000 + int(rng.integers(0, 300)) if i else ref_length - pos - a - b + 1
+            reads.append(_extra_read(rng, pos, [("M", a), ("N", gap), ("M", b)] if i != 3 else [("S", 3), ("M", a), ("N", gap), ("M", b), ("I", 2), ("M", 4)]))
+        for i in range(4):
+            reads.append(_extra_read(rng, 1, [("M", int(rng.integers(20, 120)))] if i != 2 else [("S", 4), ("M", 30), ("D", 2), ("M", 30)]))
+        for i in range(4):
+            cigar = [("M", int(rng.integers(20, 120)))] if i != 2 else [("M", 30), ("I", 1), ("M", 30), ("S", 4)]
+            reads.append(_extra_read(rng, ref_length - sum(n for op, n in cigar if op == "M") + 1, cigar))
+    ids = []
+    for i, r in enumerate(reads):
+        pool = window_ids(r["pos"])
+        ids.append(-1 if (i % 7 == 3 and not tag_all) else int(pool[int(rng.integers(0, len(pool)))]))
+    return reads, ids
+
+
+def further_tagged_reads(seed, lo, hi, n=60, shift=0):
+    """A later batch over [lo, hi): ordinary reads, every one tagged; shift: the ids of the window `shift` windows further on (other ids over the
+    same positions, for a store that holds nothing else there)"""
+    from tests.test_read_store import random_reads
+    rng = np.random.default_rng(seed)
+    reads = random_reads(rng, n, lo, hi, sort=True)
+    ids = []
+    for r in reads:
+        pool = window_ids(r["pos"] + shift * WINDOW)
+        ids.append(int(pool[int(rng.integers(0, len(pool)))]))
+    return reads, ids
+
+
+PLANTED_THRESHOLDS = (0.01, 0.001, 0.05, 0.2, 0.5)
+PLANTED_SEEDS = [(31, 0.01), (32, 0.001), (33, 0.05), (34, 0.2), (35, 0.5)]     # (seed, threshold)
+MIN_FREQUENCY = 0.01               # the callers' default (MinimumFrequency)
+VARIANT_FREQUENCIES = (0.005, 0.01, 0.02, 0.05, 0.08, 0.1, 0.12, 0.3)     # seeded_sets' (tests/test_amplicon_cpu.py)
+DEPLETION = (0.0, 0.3, 0.6, 0.8, 1.0, 1.1)
+DEPTHS, DEPTH_P = (30, 60, 120, 250, 500, 1000), (.22, .22, .22, .18, .10, .06)
+
+
+def _poisson_tail(k, lam):
+    """P(X >= k) for X ~ Poisson(lam)"""
+    import math
+    term, cdf = math.exp(-lam), 0.0
+    for i in range(k):
+        cdf += term
+        term *= lam / (i + 1)
+    return max(0.0, 1.0 - cdf)
+
+
+def is_special(p):
+    """The first, the last and the last-but-one position of a 64-locus tile, or the first position of a block.  Tiles start at a block's
+    first position and blocks at 1 + a multiple of 1000: in the first block these are p % 64 in (1, 0, 63)."""
+    offset = (p - 1) % 1000
+    return offset % 64 in (0, 63, 62)
+
+
+def planted_scenario(seed, threshold):
+    """filter_scenario at large: eight regions of 100-base reads — one at position 1, six between 905 and 1780 (the block edge 1000 / 1001 inside
+    the first) with 1..6 amplicons in a seeded order, one that ends on the reference's last base — every amplicon at its own depth (tens to
+    about a thousand) and its own offset, untagged reads (20-40 and a twentieth of the region's depth), two low-quality bases a read.  Each region has about ten planted
+    loci at least 7 apart, the tile edges and block starts of the region among them.  A locus draws one variant frequency and a depletion
+    factor per amplicon (seeded_sets' distributions) and its carriers from them; one locus in six plants a second alternative base, one in
+    eight has its carriers among the untagged reads; position 1, the last base and a block's first position always carry an allele of 2.5 %
+    or more.  A draw whose allele would reach 1.5 % of the depth without the support a call
+    needs (Poisson tail of the 1 % noise above 1e-3) is drawn again, so that every allele of 2 % and more has its row.
+    -> dict(ref, reads, ids (position order), threshold, loci: {position: dict(k, alts: [base...], untagged: bool)})"""
+    rng = np.random.default_rng(seed)
+    ks = [int(k) for k in rng.permutation(6) + 1]
+    starts = [1] + [905 + 150 * r + int(rng.integers(0, 16)) for r in range(6)] + [1850]
+    ks = [int(rng.integers(2, 5))] + ks + [int(rng.integers(2, 5))]
+    length = starts[-1] + 99
+    ref = reference(length)
+    all_ids = [0, 0x7FFFFFFF] + [int(x) + 1 for x in rng.choice(10 ** 6, 40, replace=False)]
+    all_ids = [all_ids[i] for i in rng.permutation(len(all_ids))]
+    reads, ids, loci = [], [], {}
+    for region, (start, k) in enumerate(zip(starts, ks)):
+        edge = region in (0, len(starts) - 1)
+        offsets = [0] * k if edge else [int(o) for o in rng.integers(0, 9, k)]
+        amps = [all_ids.pop() for _ in range(k)]
+        depths = [max(20, int(rng.choice(DEPTHS, p=DEPTH_P) * rng.uniform(0.7, 1.3))) for _ in range(k)]
+        n_untagged = int(rng.integers(20, 41)) + sum(depths) // 20
+        # the region's reads as (start, id, edits); the untagged ones last
+        members = [[(start + off, amp, {}) for _ in range(depth)] for off, amp, depth in zip(offsets, amps, depths)]
+        members.append([(start + (0 if edge else 4), -1, {}) for _ in range(n_untagged)])
+        core_lo, core_hi = (start, start + 99) if edge else (start + 8, start + 99)
+        grid = [core_lo + 9 * i + (0 if edge else int(rng.integers(0, 3))) for i in range(12)]
+        grid = [p for p in grid if p <= core_hi]
+        chosen, group = [], []
+        for p in range(core_lo, core_hi + 2):
+            if p <= core_hi and is_special(p) and not edge:
+                group.append(p)
+            elif group:
+                chosen.append(int(rng.choice(group)))
+                group = []
+        positions = sorted(set(chosen) | {p for p in grid if all(abs(p - q) >= 7 for q in chosen)})
+        total_depth = sum(depths) + n_untagged
+        for p in positions:
+            n_alts = 2 if rng.integers(0, 6) == 0 else 1
+            must = p in (1, length) or p % 1000 == 1      # position 1, the last base, a block's first position: always an allele with a row
+            untagged = bool(rng.integers(0, 8) == 0) and not must
+            alts = [b for b in "ACGT" if b != chr(ref[p - 1])]
+            alts = [alts[i] for i in rng.permutation(3)[:n_alts]]
+            free = [list(rng.permutation(len(m))) for m in members]     # reads of every group that carry no allele here yet
+            for alt in alts:
+                for _ in range(50):
+                    if untagged:
+                        carriers = [0] * k + [int(rng.integers(n_untagged // 4, n_untagged // 2))]
+                    else:
+                        vf = float(rng.choice(VARIANT_FREQUENCIES))
+                        keep = rng.choice(DEPLETION, size=k)
+                        carriers = [int(min(len(free[j]), rng.poisson(depths[j] * vf * keep[j]))) for j in range(k)] + [0]
+                    s = sum(carriers)
+                    if must and alt == alts[0] and s < 0.025 * total_depth:
+                        continue
+                    if s == 0 or s < 0.015 * total_depth or _poisson_tail(s, MIN_FREQUENCY * total_depth) <= 1e-3:
+                        break
+                else:
+                    carriers = [0] * (k + 1)
+                for j, c in enumerate(carriers):
+                    for _ in range(c):
+                        members[j][free[j].pop()][2][p] = alt
+            loci[p] = dict(k=k, alts=alts, untagged=untagged)
+        for m in members:
+            for i, (pos, amp, edits) in enumerate(m):
+                low = set(int(x) for x in rng.integers(pos, pos + 100, 2))
+                reads.append(_read(ref, pos, [("M", 100)], reverse=bool(i & 1), edits=edits, low=low))
+                ids.append(amp)
+    order = sorted(range(len(reads)), key=lambda i: reads[i]["pos"])
+    return dict(ref=ref, reads=[reads[i] for i in order], ids=[ids[i] for i in order], threshold=threshold, loci=loci)
+
+
+def lifecycle_case(seed, exotic=False, tag_all=False):
+    """What the counts fuzz adds over a store's life: the reads of random_tagged_reads; a position to call up to that is no block edge and
+    the floor that call leaves (the first position of the block it lies in); a tagged batch that straddles the floor (its first reads start
+    below it, in the block the call cleared); and, for after the final call, a batch with other ids over the same positions."""
+    reads, ids = random_tagged_reads(seed, exotic=exotic, tag_all=tag_all)
+    call_at = int(np.random.default_rng(seed + 1).integers(1100, 1600))
+    floor = call_at // 1000 * 1000 + 1
+    return dict(reads=reads, ids=ids, call_at=call_at, floor=floor, ahead=further_tagged_reads(seed + 2, floor - 40, floor + 400),
+                fresh=further_tagged_reads(seed + 3, FUZZ_LO, FUZZ_HI, n=120, shift=1))

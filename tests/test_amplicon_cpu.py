@@ -194,3 +194,137 @@ def test_no_decision_of_the_gpu_scenarios_sits_on_its_threshold():
             continue
         alt = S.OTHER[chr(ref[position - 1])]
         assert R.bias_detected(support.get(position, {}).get(alt, {}), coverage[position], S.THRESHOLD) is want, position
+
+
+def test_the_haploid_scenario_decides_as_it_says_and_off_its_threshold():
+    from tests import amplicon_cases as S
+    ref, reads, ids = S.haploid_scenario()
+    coverage, support = R.amplicon_counts(reads, S.names_of(ids))
+    assert sorted(p for p, by in support.items() if set(by) != {chr(ref[p - 1])}) == sorted(S.HAPLOID_PLANTED)
+    for position, want in S.HAPLOID_PLANTED.items():
+        alt = S.OTHER[chr(ref[position - 1])]
+        assert sum(support[position][alt].values()) > 0.8 * sum(coverage[position].values())     # the locus' one allele for the haploid genotyper
+        assert R.bias_detected(support[position][alt], coverage[position], S.THRESHOLD) is want, position
+        assert R.margin_to_threshold(support[position][alt], coverage[position], S.THRESHOLD) > 1e-6, position
+
+
+# ---- the seeded generators of the device fuzz (tests/amplicon_cases.py): what they promise, from the data and the Python statement alone ----
+
+_planted_cache = {}
+
+
+def planted(seed, threshold):
+    """(scenario, coverage, support) of a planted seed, made once"""
+    from tests import amplicon_cases as S
+    if (seed, threshold) not in _planted_cache:
+        sc = S.planted_scenario(seed, threshold)
+        _planted_cache[seed, threshold] = (sc,) + R.amplicon_counts(sc["reads"], S.names_of(sc["ids"]))
+    return _planted_cache[seed, threshold]
+
+
+def test_no_seed_of_the_generators_reaches_a_seventh_amplicon():
+    """R.amplicon_counts raises TooManyAmplicons on a seventh id: it must not, for every listed seed, in every state the device tests
+    bring a store to (the reads alone, with the batch that straddles the floor, the fresh batch alone; the all-tagged exotic variant)."""
+    from tests import amplicon_cases as S
+    for seed in S.TAGGED_SEEDS:
+        for kw in ({}, dict(exotic=True, tag_all=True)):
+            case = S.lifecycle_case(seed, **kw)
+            text = lambda reads: [dict(r, seq=bytes(r["seq"]).decode("latin-1")) for r in reads]
+            R.amplicon_counts(text(case["reads"] + case["ahead"][0]), S.names_of(case["ids"] + case["ahead"][1]))
+            R.amplicon_counts(text(case["fresh"][0]), S.names_of(case["fresh"][1]))
+    for seed, threshold in S.PLANTED_SEEDS:
+        planted(seed, threshold)
+
+
+def test_random_tagged_reads_contain_what_they_promise():
+    from tests import amplicon_cases as S
+    for seed in S.TAGGED_SEEDS:
+        reads, ids = S.random_tagged_reads(seed)
+        assert len(reads) == 614 and len(ids) == len(reads)
+        ops = [set(op for op, _ in r["cigar"]) for r in reads]
+        for op in "MIDSNHP=X":
+            assert any(op in o for o in ops), (seed, op)
+        assert any(r["cigar"][-1][0] == "D" for r in reads) and any(r["cigar"][0][0] == "D" for r in reads)   # terminal deletions
+        assert any(b"N" in r["seq"] for r in reads) and {10, 25, 37, 200} <= set(q for r in reads for q in r["quals"])
+        ordinary = [r for r in reads if S.ref_span(r) <= 0xFFFF]
+        assert len(reads) - len(ordinary) == 6 and max(S.ref_span(r) for r in ordinary) < S.WINDOW
+        assert sum(r["pos"] == 1 for r in reads) == 4
+        assert sum(r["pos"] + S.ref_span(r) - 1 == S.FUZZ_REF_LENGTH for r in reads) == 5 and all(r["pos"] + S.ref_span(r) - 1 <= S.FUZZ_REF_LENGTH for r in reads)
+        untagged = sum(i == -1 for i in ids)
+        assert len(ids) // 9 < untagged < len(ids) // 5 and min(ids) == -1
+        assert {0, 0x7FFFFFFF} <= set(ids)
+        coverage, _ = R.amplicon_counts(reads, S.names_of(ids))
+        assert {len(v) for v in coverage.values()} == {1, 2, 3, 4, 5, 6}, seed
+        assert 1 in coverage and S.FUZZ_REF_LENGTH in coverage
+        # tile edges and a block edge inside the range, and reads on both sides of them
+        assert all(p in coverage for p in (1000, 1001, 1064, 1065, 1128, 1129))
+        # every read tagged: the variant whose counts are held to the caller's own
+        assert min(S.random_tagged_reads(seed, exotic=True, tag_all=True)[1]) >= 0
+
+
+def test_no_decision_of_the_planted_scenarios_sits_on_its_threshold():
+    """The margin of test_no_case_sits_on_its_threshold for every (position, base) with tagged or untagged support in every planted
+    scenario, none left out (a seed that puts one inside the margin is replaced in the list)."""
+    from tests import amplicon_cases as S
+    assert sorted(t for _, t in S.PLANTED_SEEDS) == sorted(S.PLANTED_THRESHOLDS)
+    for seed, threshold in S.PLANTED_SEEDS:
+        sc, coverage, support = planted(seed, threshold)
+        total = R.amplicon_counts(sc["reads"], [0] * len(sc["reads"]))[1]
+        n = 0
+        for position, by_base in total.items():
+            for base in by_base:
+                if base != chr(sc["ref"][position - 1]):
+                    n += 1
+                    assert R.margin_to_threshold(support.get(position, {}).get(base, {}), coverage.get(position, {}), threshold) > 1e-6, (seed, position, base)
+        assert n >= 80, (seed, n)
+
+
+def test_planted_scenarios_reach_every_answer_at_every_number_of_amplicons():
+    """Over the listed seeds the statement decides the planted alleles 185 times True, 153 times False and 143 times None (asked: 40 / 40 / 10);
+    by the number of amplicons at the locus, True: {2: 25, 3: 29, 4: 55, 5: 36, 6: 40}, False: {2: 44, 3: 41, 4: 47, 5: 9, 6: 12}.
+    The loci hold position 1, the reference's last base, first / last / last-but-one positions of tiles, a block's first position, loci
+    with two alternative bases and loci whose carriers have no tag; every region size 1..6 occurs in every scenario."""
+    from tests import amplicon_cases as S
+    counts = {True: {}, False: {}, None: {}}
+    kinds = set()
+    for seed, threshold in S.PLANTED_SEEDS:
+        sc, coverage, support = planted(seed, threshold)
+        assert 4000 <= len(sc["reads"]) <= 8000 and all(S.ref_span(r) == 100 for r in sc["reads"])
+        assert {v["k"] for v in sc["loci"].values()} == {1, 2, 3, 4, 5, 6}
+        positions = sorted(sc["loci"])
+        assert len(positions) >= 70 and min(b - a for a, b in zip(positions, positions[1:])) >= 7
+        assert 1 in sc["loci"] and len(sc["ref"]) in sc["loci"] and 1001 in sc["loci"]
+        for position, locus in sc["loci"].items():
+            k = len(coverage[position])
+            assert k == locus["k"], (seed, position)
+            kinds.add(("tile", (position - 1) % 1000 % 64))
+            kinds.add(("alts", len(locus["alts"])))
+            kinds.add(("untagged", locus["untagged"]))
+            for alt in locus["alts"]:
+                answer = R.bias_detected(support.get(position, {}).get(alt, {}), coverage[position], threshold)
+                assert not (locus["untagged"] or k == 1) or answer is None
+                counts[answer][k] = counts[answer].get(k, 0) + 1
+    assert {("tile", 0), ("tile", 62), ("tile", 63), ("alts", 2), ("untagged", True)} <= kinds
+    n = {answer: sum(by_k.values()) for answer, by_k in counts.items()}
+    assert n[True] >= 40 and n[False] >= 40 and n[None] >= 10, n
+    assert set(counts[True]) == {2, 3, 4, 5, 6} and set(counts[False]) == {2, 3, 4, 5, 6}, counts
+    assert (n[True], n[False], n[None]) == (185, 153, 143), n     # the docstring's figures
+
+
+def test_decision_does_not_depend_on_the_order_of_the_amplicons():
+    """The device claims a locus' slots in arrival order, so amplicon::bias sees the amplicons in an order that differs from run to run
+    (amplicon_bias.h: no decision depends on it).  On the host: the same decision and the same multiset of chances for the arrays as
+    drawn, reversed and under three seeded permutations."""
+    rng = np.random.default_rng(20260101)
+    n_decided = 0
+    for support, coverage, threshold in seeded_sets():
+        detected, chance = engine.amplicon_bias(support, coverage, threshold)
+        k = len(coverage)
+        for order in [np.arange(k)[::-1]] + [rng.permutation(k) for _ in range(3)]:
+            again, chance_again = engine.amplicon_bias([support[i] for i in order], [coverage[i] for i in order], threshold)
+            assert again is detected, (support, coverage, threshold, list(order))
+            if detected is not None:
+                assert sorted(chance_again) == sorted(chance), (support, coverage, threshold, list(order))
+                assert [chance_again[j] for j in np.argsort(order)] == list(chance)
+        n_decided += detected is not None
+    assert n_decided > N_SEEDED // 2
