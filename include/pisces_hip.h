@@ -408,9 +408,15 @@ int32_t pisces_hip_get_counts(PiscesHip* h, int32_t start_position, int32_t n, i
  * caller applies the anchor window, AlleleCountHelper.GetAnchorAdjustedTotalQuality).  Served by any handle, not only NoiseModel.Window.
  * The device accumulates in fixed point: each cell is the true sum rounded once, identical from run to run. */
 int32_t pisces_hip_get_base_quality_sums(PiscesHip* h, int32_t start_position, int32_t n, double* out);
-/* IAlleleSource.GetGappedMnvRefCount (IAlleleSource.cs:19): what pisces_hip_add_gapped_mnv_ref registered for the position, else 0 */
+/* IAlleleSource.GetGappedMnvRefCount (IAlleleSource.cs:19; RegionStateManager.cs:256-261): what pisces_hip_add_gapped_mnv_ref (or a flush,
+ * for the gaps of its callable MNVs) registered for the position and no flush has retired with the position's block since; 0 for every
+ * other position > 0, however far out (no block: no count, as for the allele counts).  position <= 0: PISCES_E_INVALID_ARG, *count
+ * untouched (GetBlock's "Position must be greater than 0.", :363-364).  The handle is the manager, its blocks are made on demand: the
+ * single RegionState's "outside the region" (RegionState.cs:86-92, 375-381) has no counterpart here. */
 int32_t pisces_hip_get_gapped_mnv_ref(PiscesHip* h, int32_t position, int32_t* count);
-/* IAlleleSource.AddGappedMnvRefCount (RegionStateManager.cs:74-81) */
+/* IAlleleSource.AddGappedMnvRefCount (RegionStateManager.cs:74-81): counts[i] is added to what positions[i] holds (0 changes nothing, a
+ * position not named keeps its count); every position > 0 is accepted and makes its block.  A position <= 0 anywhere in the call:
+ * PISCES_E_INVALID_ARG and nothing of the call is added. */
 int32_t pisces_hip_add_gapped_mnv_ref(PiscesHip* h, const int32_t* positions, const int32_t* counts, int32_t n);
 /* host-side candidates (insertion / deletion) found so far with position <= up_to (< 0 = all)
  * (IStateManager.GetCandidatesToProcess for the host collapser). alleles = byte pool; out may be NULL to count. */

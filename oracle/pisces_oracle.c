@@ -976,6 +976,14 @@ static int32_t get_gapped_mnv_ref(const OrcState* s, int32_t position)
 {
     return in_region(s, position) ? s->gapped[position - s->start_position] : 0;
 }
+/* RegionState.GetGappedMnvRefCount (RegionState.cs:375-381) of the window as one block: a position outside it is an ArgumentException
+ * (PISCES_E_INVALID_ARG, *count untouched); RegionState.AddGappedMnvRefCount :86-92 drops such a position (orc_add_gapped_mnv_ref). */
+int32_t orc_get_gapped_mnv_ref(const OrcState* s, int32_t position, int32_t* count)
+{
+    if (!in_region(s, position)) return PISCES_E_INVALID_ARG;
+    *count = s->gapped[position - s->start_position];
+    return 0;
+}
 
 /* CandidateAllele.Equals (CandidateAllele.cs:58-68) */
 static int candidate_equals(const OrcCandidate* a, const OrcCandidate* b)
@@ -996,16 +1004,25 @@ void orc_track_blocks(OrcState* s, int32_t block_size)
     s->max_allele_endpoint = (int32_t*)calloc((size_t)s->n_blocks, sizeof(int32_t));
 }
 
-int32_t orc_add_candidate(OrcState* s, const OrcCandidate* c)
+static int32_t add_candidate_ref_length(OrcState* s, const OrcCandidate* c, int32_t ref_length);
+int32_t orc_add_candidate(OrcState* s, const OrcCandidate* c) { return add_candidate_ref_length(s, c, (int32_t)strlen(c->ref)); }
+/* the same for a candidate whose reference allele does not fit ORC_MAX_ALLELE (the 3500-base deletion of RegionStateManagerTests.cs:739):
+ * c->ref holds its first bytes, ref_length its length, which is all UpdateMaxPosition reads of it */
+int32_t orc_add_candidate_ref_length(OrcState* s, const OrcCandidate* c, int32_t ref_length)
+{
+    if (ref_length < (int32_t)strlen(c->ref)) return PISCES_E_INVALID_ARG;
+    return add_candidate_ref_length(s, c, ref_length);
+}
+static int32_t add_candidate_ref_length(OrcState* s, const OrcCandidate* c, int32_t ref_length)
 {
     if (c->category == PISCES_CAT_REFERENCE) return PISCES_E_INVALID_ARG;
     if (!in_region(s, c->position)) return PISCES_E_INVALID_ARG;
     int li = c->position - s->start_position;
     if (s->block_size > 0) {   /* RegionState.UpdateMaxPosition :203-223 (before the merge, for every candidate handed in) */
         int otherEnd = 0;
-        if (c->category == PISCES_CAT_DELETION) otherEnd = c->position + (int)strlen(c->ref);
+        if (c->category == PISCES_CAT_DELETION) otherEnd = c->position + ref_length;
         else if (c->category == PISCES_CAT_INSERTION) otherEnd = c->position + 1;
-        else if (c->category == PISCES_CAT_MNV) otherEnd = c->position + (int)strlen(c->ref) - 1;
+        else if (c->category == PISCES_CAT_MNV) otherEnd = c->position + ref_length - 1;
         int32_t* m = &s->max_allele_endpoint[(c->position - 1) / s->block_size + 1 - s->first_block_key];
         if (otherEnd > *m) *m = otherEnd;
     }
@@ -2322,8 +2339,16 @@ int32_t orc_next_batch(OrcState* s, int32_t up_to_position, int32_t* first_posit
 /* DoneProcessing :336-360 for the blocks up to last_position */
 void orc_done_processing(OrcState* s, int32_t last_position)
 {
+    /* the blocks leave _regionLookup :344-347: GetAlleleCount / GetGappedMnvRefCount of their positions find no block and return 0
+     * (:222-226, :256-261; RegionStateManagerTests.DoneProcessing :744-780) */
+    const size_t per = (size_t)6 * 3 * (size_t)s->n_anchor_idx;
     for (int li = 0; li < s->n_loci; li++)
-        if (s->start_position + li <= last_position) s->cand_head[li] = s->cand_tail[li] = -1;
+        if (s->start_position + li <= last_position) {
+            s->cand_head[li] = s->cand_tail[li] = -1;
+            memset(s->counts + (size_t)li * per, 0, per * sizeof(int32_t));
+            memset(s->sumq + (size_t)li * per, 0, per * sizeof(double));
+            s->gapped[li] = 0;
+        }
     const int key = (last_position - 1) / s->block_size + 1;
     if (key + 1 > s->next_block_key) s->next_block_key = key + 1;
 }
@@ -2336,35 +2361,13 @@ int64_t orc_call_range(OrcState* s, const uint8_t* ref_bases, int64_t ref_len, c
     return orc_call_range_up_to(s, ref_bases, ref_len, cfg, first_position, last_position, -1, out, capacity, full_out, total_num_called);
 }
 
-/* up_to_position >= 0: a batch made while reads are still arriving (GetCandidatesToProcess(upToPosition)); when an allele of the cleared
- * blocks reaches past last_position the collapsable candidates of the following blocks join it (AddCollapsableFromOtherBlocks). */
-int64_t orc_call_range_up_to(OrcState* s, const uint8_t* ref_bases, int64_t ref_len, const PiscesHipConfig* cfg, int32_t first_position,
-                             int32_t last_position, int32_t up_to_position, PiscesCalledAllele* out, int64_t capacity, OrcCalled* full_out,
-                             int64_t* total_num_called)
+/* RegionState.GetAllCandidates :393-450: Reference candidates over the block (gVCF; the window stands for the intervals), or — not a
+ * gVCF, forced alleles given — at the positions of the forced alleles (CreateIntervalsFromAllels :455-468), there with or without
+ * coverage (IntervalsInUse != null).  Appends to list[*n) (grown as needed) and returns it. */
+static OrcCandidate* add_reference_candidates(const OrcState* s, const uint8_t* ref_bases, int64_t ref_len, const PiscesHipConfig* cfg,
+                                              int32_t first_position, int32_t last_position, OrcCandidate* list, int64_t* n_io, int64_t* cap_io)
 {
-    /* one batch of the block schedule: the candidates and Reference candidates of [first_position, last_position] (whole blocks),
-     * MaxClearedPosition = last_position (RegionStateManager.cs:283-334).  What the batch pushes past it (MNV leftovers) goes back to
-     * the state and is found by the next range; processed candidates are removed (DoneProcessing). */
-    orc_add_forced_as_candidates(s, up_to_position);   /* SmallVariantCaller.cs:101-108: before Call(upTo) */
-    int64_t cap = (int64_t)s->n_cands + 64;
-    OrcCandidate* list = (OrcCandidate*)malloc(sizeof(OrcCandidate) * (size_t)cap);
-    int32_t from_other_blocks = 0;
-    int64_t n = orc_batch_candidates(s, first_position, last_position, up_to_position, list, (int32_t)cap, &from_other_blocks);
-    for (int li = 0; li < s->n_loci; li++) {   /* DoneProcessing :336-360 (what the batch hands back goes to later blocks) */
-        const int position = s->start_position + li;
-        if (position >= first_position && position <= last_position) s->cand_head[li] = s->cand_tail[li] = -1;
-    }
-    if (cfg->collapse) {   /* AlleleCaller.Call :50-58: candidates = _collapser.Collapse(batch.GetCandidates(), source, MaxClearedPosition) */
-        OrcCandidate* back = from_other_blocks ? (OrcCandidate*)malloc(sizeof(OrcCandidate) * (size_t)(n > 0 ? n : 1)) : NULL;
-        int32_t n_back = 0;
-        n = orc_collapse(list, (int32_t)n, s, cfg->collapse_freq_threshold, cfg->collapse_freq_ratio_threshold, g_exclude_mnvs, 1,
-                         cfg->expect_stitched_reads, from_other_blocks ? last_position : -1, NULL, back, &n_back);
-        for (int i = 0; i < n_back; i++) orc_add_candidate(s, &back[i]);   /* source.AddCandidates(notClearedVariants) :67-75 */
-        free(back);
-    }
-    /* RegionState.GetAllCandidates :393-450: Reference candidates over the block (gVCF; the window stands for the intervals), or — not a
-     * gVCF, forced alleles given — at the positions of the forced alleles (CreateIntervalsFromAllels :455-468), there with or without
-     * coverage (IntervalsInUse != null) */
+    int64_t n = *n_io, cap = *cap_io;
     const int refs_at_forced_only = !cfg->include_reference_calls && s->n_forced > 0;
     if ((cfg->include_reference_calls || refs_at_forced_only) && ref_bases) {
         for (int li = 0; li < s->n_loci; li++) {
@@ -2398,6 +2401,58 @@ int64_t orc_call_range_up_to(OrcState* s, const uint8_t* ref_bases, int64_t ref_
             }
         }
     }
+    *n_io = n;
+    *cap_io = cap;
+    return list;
+}
+
+/* RegionState.GetAllCandidates :383-453 over [first_position, last_position] of the window: the candidates by position, each position in
+ * arrival order, then the Reference candidates (cfg->include_reference_calls; inside the interval set of orc_set_intervals; a position
+ * without coverage only with cfg->emit_zero_coverage_refs, which a caller sets when it has an interval set, :446).  Returns the count
+ * (out filled up to capacity). */
+int32_t orc_get_all_candidates(OrcState* s, const uint8_t* ref_bases, int64_t ref_len, const PiscesHipConfig* cfg, int32_t first_position,
+                               int32_t last_position, OrcCandidate* out, int32_t capacity)
+{
+    int64_t cap = (int64_t)s->n_cands + 64, n = 0;
+    OrcCandidate* list = (OrcCandidate*)malloc(sizeof(OrcCandidate) * (size_t)cap);
+    for (int li = 0; li < s->n_loci; li++) {
+        const int position = s->start_position + li;
+        if (position < first_position || position > last_position) continue;
+        for (int i = s->cand_head[li]; i >= 0; i = s->cands[i].next) list[n++] = s->cands[i];
+    }
+    list = add_reference_candidates(s, ref_bases, ref_len, cfg, first_position, last_position, list, &n, &cap);
+    for (int64_t i = 0; i < n && i < capacity; i++) out[i] = list[i];
+    free(list);
+    return (int32_t)n;
+}
+
+/* up_to_position >= 0: a batch made while reads are still arriving (GetCandidatesToProcess(upToPosition)); when an allele of the cleared
+ * blocks reaches past last_position the collapsable candidates of the following blocks join it (AddCollapsableFromOtherBlocks). */
+int64_t orc_call_range_up_to(OrcState* s, const uint8_t* ref_bases, int64_t ref_len, const PiscesHipConfig* cfg, int32_t first_position,
+                             int32_t last_position, int32_t up_to_position, PiscesCalledAllele* out, int64_t capacity, OrcCalled* full_out,
+                             int64_t* total_num_called)
+{
+    /* one batch of the block schedule: the candidates and Reference candidates of [first_position, last_position] (whole blocks),
+     * MaxClearedPosition = last_position (RegionStateManager.cs:283-334).  What the batch pushes past it (MNV leftovers) goes back to
+     * the state and is found by the next range; processed candidates are removed (DoneProcessing). */
+    orc_add_forced_as_candidates(s, up_to_position);   /* SmallVariantCaller.cs:101-108: before Call(upTo) */
+    int64_t cap = (int64_t)s->n_cands + 64;
+    OrcCandidate* list = (OrcCandidate*)malloc(sizeof(OrcCandidate) * (size_t)cap);
+    int32_t from_other_blocks = 0;
+    int64_t n = orc_batch_candidates(s, first_position, last_position, up_to_position, list, (int32_t)cap, &from_other_blocks);
+    for (int li = 0; li < s->n_loci; li++) {   /* DoneProcessing :336-360 (what the batch hands back goes to later blocks) */
+        const int position = s->start_position + li;
+        if (position >= first_position && position <= last_position) s->cand_head[li] = s->cand_tail[li] = -1;
+    }
+    if (cfg->collapse) {   /* AlleleCaller.Call :50-58: candidates = _collapser.Collapse(batch.GetCandidates(), source, MaxClearedPosition) */
+        OrcCandidate* back = from_other_blocks ? (OrcCandidate*)malloc(sizeof(OrcCandidate) * (size_t)(n > 0 ? n : 1)) : NULL;
+        int32_t n_back = 0;
+        n = orc_collapse(list, (int32_t)n, s, cfg->collapse_freq_threshold, cfg->collapse_freq_ratio_threshold, g_exclude_mnvs, 1,
+                         cfg->expect_stitched_reads, from_other_blocks ? last_position : -1, NULL, back, &n_back);
+        for (int i = 0; i < n_back; i++) orc_add_candidate(s, &back[i]);   /* source.AddCandidates(notClearedVariants) :67-75 */
+        free(back);
+    }
+    list = add_reference_candidates(s, ref_bases, ref_len, cfg, first_position, last_position, list, &n, &cap);
     int64_t r = orc_call_candidates_max(s, list, n, ref_bases, ref_len, cfg, last_position, out, capacity, full_out, total_num_called);
     free(list);
     return r;

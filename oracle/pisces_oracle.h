@@ -120,6 +120,11 @@ const int32_t* orc_counts_ptr(const OrcState* s);                           /* [
 int32_t   orc_num_anchor_indexes(const OrcState* s);
 void      orc_add_gapped_mnv_ref(OrcState* s, int32_t position, int32_t count);
 int32_t   orc_add_candidate(OrcState* s, const OrcCandidate* c);            /* RegionState.cs:94-174 */
+int32_t   orc_add_candidate_ref_length(OrcState* s, const OrcCandidate* c, int32_t ref_length); /* a reference allele longer than ORC_MAX_ALLELE */
+int32_t   orc_get_gapped_mnv_ref(const OrcState* s, int32_t position, int32_t* count); /* RegionState.cs:375-381; outside the window: PISCES_E_INVALID_ARG */
+/* RegionState.GetAllCandidates :383-453 over [first_position, last_position]: candidates, then Reference candidates (gVCF) */
+int32_t   orc_get_all_candidates(OrcState* s, const uint8_t* ref_bases, int64_t ref_len, const PiscesHipConfig* cfg, int32_t first_position,
+                                 int32_t last_position, OrcCandidate* out, int32_t capacity);
 int32_t   orc_num_candidates(const OrcState* s);
 int32_t   orc_get_candidates(const OrcState* s, OrcCandidate* out, int32_t capacity); /* position order */
 

@@ -2610,6 +2610,7 @@ int32_t pisces_hip_get_gapped_mnv_ref(PiscesHip* h, int32_t position, int32_t* c
 {
     return abi_guard<int32_t>(h, [&]() -> int32_t {
     if (!h || !count) return PISCES_E_INVALID_ARG;
+    if (position <= 0) return fail(h, PISCES_E_INVALID_ARG, "Position must be greater than 0.");   // GetBlock (RegionStateManager.cs:363-364)
     auto it = h->gapped_mnv_ref.find(position);
     *count = it == h->gapped_mnv_ref.end() ? 0 : it->second;
     return PISCES_OK;
@@ -2622,8 +2623,9 @@ int32_t pisces_hip_add_gapped_mnv_ref(PiscesHip* h, const int32_t* positions, co
     if (!h) return PISCES_E_INVALID_ARG;
     if (n < 0 || (n > 0 && (!positions || !counts))) return fail(h, PISCES_E_INVALID_ARG, "add_gapped_mnv_ref: null buffer");
     { int32_t rcp = refuse_while_batch_is_open(h, "add_gapped_mnv_ref"); if (rcp) return rcp; }
-    for (int32_t i = 0; i < n; i++) {
+    for (int32_t i = 0; i < n; i++)   // (checked before anything is added: a refused call leaves the state as it was)
         if (positions[i] <= 0) return fail(h, PISCES_E_INVALID_ARG, "Position must be greater than 0.");
+    for (int32_t i = 0; i < n; i++) {
         (void)get_block(h, positions[i]);   // GetBlock(position) creates the block (RegionStateManager.cs:78)
         h->gapped_mnv_ref[positions[i]] += counts[i];
     }

@@ -121,6 +121,12 @@ def _load():
         "orc_num_anchor_indexes": (i32, [C.c_void_p]),
         "orc_add_gapped_mnv_ref": (None, [C.c_void_p, i32, i32]),
         "orc_add_candidate": (i32, [C.c_void_p, P(OrcCandidate)]),
+        "orc_add_candidate_ref_length": (i32, [C.c_void_p, P(OrcCandidate), i32]),
+        "orc_get_gapped_mnv_ref": (i32, [C.c_void_p, i32, P(i32)]),
+        "orc_get_all_candidates": (i32, [C.c_void_p, P(C.c_uint8), i64, P(_abi.PiscesHipConfig), i32, i32, P(OrcCandidate), i32]),
+        "orc_set_intervals": (None, [C.c_void_p, P(i32), P(i32), i32]),
+        "orc_call_candidates_max": (i64, [C.c_void_p, P(OrcCandidate), i64, P(C.c_uint8), i64, P(_abi.PiscesHipConfig), i32, C.c_void_p, i64,
+                                          P(OrcCalled), P(i64)]),
         "orc_num_candidates": (i32, [C.c_void_p]),
         "orc_get_candidates": (i32, [C.c_void_p, P(OrcCandidate), i32]),
         "orc_find_candidates": (i32, [P(OrcRead), P(C.c_uint8), i64, i32, i32, i32, i32, i32, P(OrcCandidate), i32]),
@@ -236,8 +242,40 @@ class State:
         a = np.ctypeslib.as_array(p, shape=(self.n_loci, 6, 3, na))
         a[pos - self.start, allele, direction, anchor] = value
 
-    def add_candidate(self, cand):
+    def add_candidate(self, cand, ref_length=None):
+        """ref_length: the length of a reference allele that does not fit ORC_MAX_ALLELE (cand.ref holds its first bytes)."""
+        if ref_length is not None:
+            return lib.orc_add_candidate_ref_length(self.h, C.byref(cand), ref_length)
         return lib.orc_add_candidate(self.h, C.byref(cand))
+
+    def add_gapped_mnv_ref(self, position, count):
+        """RegionState.AddGappedMnvRefCount: a position outside the window changes nothing."""
+        lib.orc_add_gapped_mnv_ref(self.h, position, count)
+
+    def get_gapped_mnv_ref(self, position):
+        """RegionState.GetGappedMnvRefCount: ValueError (the reference's ArgumentException) for a position outside the window."""
+        v = C.c_int32(0)
+        if lib.orc_get_gapped_mnv_ref(self.h, position, C.byref(v)) != 0:
+            raise ValueError("position %d is outside the region" % position)
+        return v.value
+
+    def set_intervals(self, intervals):
+        """The ChrIntervalSet [(first, last)] (sorted, disjoint, inclusive); [] = none."""
+        s = np.ascontiguousarray([a for a, _ in intervals], np.int32)
+        e = np.ascontiguousarray([b for _, b in intervals], np.int32)
+        lib.orc_set_intervals(self.h, s.ctypes.data_as(C.POINTER(C.c_int32)), e.ctypes.data_as(C.POINTER(C.c_int32)), len(s))
+
+    def all_candidates(self, ref_bases, cfg, first=None, last=None):
+        """RegionState.GetAllCandidates over [first, last] (default: the window): the candidates, then (cfg.include_reference_calls) the
+        Reference candidates."""
+        ref = np.frombuffer(ref_bases if isinstance(ref_bases, bytes) else ref_bases.encode(), dtype=np.uint8)
+        first = self.start if first is None else first
+        last = self.start + self.n_loci - 1 if last is None else last
+        cap = lib.orc_num_candidates(self.h) + self.n_loci + 1
+        arr = (OrcCandidate * cap)()
+        n = lib.orc_get_all_candidates(self.h, ref.ctypes.data_as(C.POINTER(C.c_uint8)), len(ref), C.byref(cfg), first, last, arr, cap)
+        assert 0 <= n <= cap, n
+        return [arr[i] for i in range(n)]
 
     def candidates(self):
         n = lib.orc_num_candidates(self.h)
@@ -279,16 +317,22 @@ class State:
         return out[:n]
 
 
-def call_candidates(state, cands, cfg, ref_bases=b""):
-    """AlleleCaller.Call over an explicit candidate batch; returns (records, full OrcCalled list, TotalNumCalled)."""
+def call_candidates(state, cands, cfg, ref_bases=b"", max_cleared_position=None):
+    """AlleleCaller.Call over an explicit candidate batch; returns (records, full OrcCalled list, TotalNumCalled).  max_cleared_position:
+    the batch's MaxClearedPosition (default: the last position of the state's window); what the call hands to the next block is in
+    state.candidates() afterwards."""
     ref = np.frombuffer(ref_bases, dtype=np.uint8) if len(ref_bases) else np.zeros(1, np.uint8)
     arr = (OrcCandidate * max(len(cands), 1))(*cands)
     cap = len(cands) + 16
     out = np.zeros(cap, dtype=_abi.CALLED_ALLELE_DTYPE)
     full = (OrcCalled * cap)()
     total = C.c_int64(0)
-    n = lib.orc_call_candidates(state.h, arr, len(cands), ref.ctypes.data_as(C.POINTER(C.c_uint8)), len(ref_bases), C.byref(cfg),
-                                out.ctypes.data, cap, full, C.byref(total))
+    if max_cleared_position is None:
+        n = lib.orc_call_candidates(state.h, arr, len(cands), ref.ctypes.data_as(C.POINTER(C.c_uint8)), len(ref_bases), C.byref(cfg),
+                                    out.ctypes.data, cap, full, C.byref(total))
+    else:
+        n = lib.orc_call_candidates_max(state.h, arr, len(cands), ref.ctypes.data_as(C.POINTER(C.c_uint8)), len(ref_bases), C.byref(cfg),
+                                        max_cleared_position, out.ctypes.data, cap, full, C.byref(total))
     assert n >= 0, n
     return out[:n], [full[i] for i in range(n)], total.value
 

@@ -10,7 +10,7 @@ import pytest
 
 from pisces_amd import _abi
 from tests import orc
-from tests.test_read_store import env
+from tests.test_read_store import STORE_MODES, env
 
 pytestmark = pytest.mark.gpu
 G = os.path.join(os.path.dirname(__file__), "golden")
@@ -341,6 +341,29 @@ def test_get_allele_count_reference_scenarios(torch_cuda):
         assert c.GetAlleleCount(1001, _abi.ALLELE_A, _abi.DIR_FORWARD) == 2
         assert c.GetAlleleCount(1001, _abi.ALLELE_A, _abi.DIR_FORWARD, minAnchor=1) == \
             st.get_allele_count(1001, _abi.ALLELE_A, _abi.DIR_FORWARD, 1)
+
+
+_DELETIONS = json.load(open(os.path.join(G, "region_state.json")))["deletions"]
+# every way reads enter the library: host reads into the read store (its placements of tests/test_read_store.py), host reads into the
+# observation log, reads that lie in device memory
+_READ_WAYS = dict([("store: " + m, ("host", dict(PISCES_HIP_READ_PATH=None, **kw))) for m, kw in STORE_MODES.items()] +
+                  [("observation log", ("host", dict(PISCES_HIP_READ_PATH="log"))), ("device reads", ("device", dict(PISCES_HIP_READ_PATH=None)))])
+
+
+@pytest.mark.parametrize("way", list(_READ_WAYS))
+@pytest.mark.parametrize("sc", _DELETIONS["scenarios"], ids=lambda s: s["name"])
+def test_get_allele_count_deletion_scenarios(torch_cuda, sc, way):
+    """RegionStateManagerTests.AddAndGetAlleleCounts_Deletions (:597-704) through AddAlleleCounts / AddDeviceReads + GetAlleleCount: a
+    deletion inside a read, behind a soft clip at its start and at its end is counted at every position it spans, with the bases at the
+    minimum quality; every asserted cell, the zero cells on both sides included."""
+    from pisces_amd import engine
+    how, environ = _READ_WAYS[way]
+    with env(**environ):
+        with engine.HipVariantCaller(_abi.default_config(min_base_call_quality=_DELETIONS["min_quality"], noise_level=25)) as c:
+            reads = [_read_dict(r, _DELETIONS["min_quality"]) for r in sc["reads"]]
+            (c.AddDeviceReads if how == "device" else c.AddAlleleCounts)(reads)
+            got = [[pos, a, d, c.GetAlleleCount(pos, ALLELE[a], DIR[d])] for pos, a, d, _ in sc["expect"]]
+    assert got == sc["expect"]
 
 
 def test_streaming_protocol_matches_oracle_and_block_schedule(torch_cuda):

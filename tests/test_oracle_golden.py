@@ -912,3 +912,181 @@ def test_diploid_locus_processor_cases():
     # no forced allele: nothing changes (Process returns early)
     assert orc.diploid_locus_process([dict(category=INS, genotype=_abi.GT_HET_ALT_REF, gq=40), dict(category=SNV, genotype=_abi.GT_HOM_ALT, gq=7)]) == \
         [(_abi.GT_HET_ALT_REF, 40), (_abi.GT_HOM_ALT, 7)]
+
+
+# ---- the reference's tables on the caller / region-state / MNV path (tests/golden/README.md: file:line of each) --------------------
+@pytest.mark.parametrize("sc", load("region_state.json")["deletions"]["scenarios"], ids=lambda s: s["name"])
+def test_add_and_get_allele_counts_deletions(sc):
+    """RegionStateManagerTests.AddAndGetAlleleCounts_Deletions (:597-704): deletions are counted at every position they span — inside a
+    read, behind a soft clip at its start, at its end — with the bases at the minimum quality; every asserted cell, the zeros included."""
+    g = load("region_state.json")["deletions"]
+    st = orc.State(900, 300, min_bq=g["min_quality"])
+    for rd in sc["reads"]:
+        assert st.add_allele_counts(_mk(rd, g["min_quality"])) == 0
+    for pos, a, d, n in sc["expect"]:
+        assert st.get_allele_count(pos, ALLELE[a], DIR[d]) == n, (pos, a, d)
+
+
+def test_done_processing_clears_blocks_and_holds_the_spanned_ones():
+    """RegionStateManagerTests.DoneProcessing (:707-781): GetCandidatesToProcess(upTo) + DoneProcessing per upTo; a cleared block's
+    counts read 0, the block whose deletion ends past upTo and the block behind it keep theirs."""
+    g = load("done_processing.json")
+    st = orc.State(1, 9000)
+    st.track_blocks(g["block_size"])
+    for rd in g["reads"]:
+        assert st.add_allele_counts(_mk(rd, 30)) == 0
+    for pos, a, d, n in g["expect_before"]:
+        assert st.get_allele_count(pos, ALLELE[a], DIR[d]) == n, (pos, a, d)
+    for c in g["candidates"]:
+        if "ref_length" in c:
+            cand = orc.make_candidate(c["pos"], _CAT[c["category"]], c["ref_base"] * (orc.ORC_MAX_ALLELE - 1), c["alt"], support=tuple(c["support"]))
+            assert st.add_candidate(cand, ref_length=c["ref_length"]) == 0
+        else:
+            assert st.add_candidate(orc.make_candidate(c["pos"], _CAT[c["category"]], c["ref"], c["alt"], support=tuple(c["support"]))) == 0
+    for step in g["steps"]:
+        b = st.next_batch(step["up_to"])
+        assert b is not None, step        # every upTo of the test lies in another block than the one before: a batch each time
+        if b:
+            st.done_processing(b[1])
+        for pos, a, d, n in step["expect"]:
+            assert st.get_allele_count(pos, ALLELE[a], DIR[d]) == n, (step["up_to"], pos)
+
+
+def test_gapped_mnv_ref_counts_add_and_get():
+    """RegionStateManagerTests.AddAndGetGappedMnvRefCount (:136-169) and RegionStateTests.AddAndGetGappedMnvReferenceCounts (+ _Errors)
+    (:282-325): counts add up per position, an add of 0 and positions not named change nothing, an add outside the region is dropped and
+    a get outside it throws."""
+    g = load("gapped_mnv_ref.json")
+    st = orc.State(1, 25000)
+    for step in g["manager"]["steps"]:
+        for pos, n in step["add"]:
+            st.add_gapped_mnv_ref(pos, n)
+        for pos, n in step["expect"]:
+            assert st.get_gapped_mnv_ref(pos) == n, pos
+    r = g["region"]
+    st = orc.State(r["start"], r["end"] - r["start"] + 1)
+    for step in r["steps"]:
+        for pos, n in step["add"]:
+            st.add_gapped_mnv_ref(pos, n)
+        for pos, n in step["expect"]:
+            assert st.get_gapped_mnv_ref(pos) == n, pos
+    e = g["region_errors"]
+    st = orc.State(e["start"], e["end"] - e["start"] + 1)
+    for pos, n in e["add"]:
+        st.add_gapped_mnv_ref(pos, n)
+    everything = lambda: [st.get_gapped_mnv_ref(p) for p in range(e["start"], e["end"] + 1)]
+    before = everything()
+    st.add_gapped_mnv_ref(*e["add_outside"])
+    assert everything() == before
+    nonzero = dict(map(tuple, e["expect_all_after"]["nonzero"]))
+    assert before == [nonzero.get(p, 0) for p in range(e["start"], e["end"] + 1)]
+    with pytest.raises(ValueError):
+        st.get_gapped_mnv_ref(e["get_throws"])
+
+
+def _region_candidates_state(g, with_intervals):
+    st = orc.State(g["region"][0], g["region"][1] - g["region"][0] + 1)
+    for c in g["candidates"]:
+        assert st.add_candidate(orc.make_candidate(c["pos"], _CAT[c["category"]], c["ref"], c["alt"], support=tuple(c["support"]))) == 0
+    for row in g["counts"]:
+        st.set_count(row["pos"], ALLELE[row["allele"]], DIR[row["dir"]], g["anchor_index"], row["n"])
+    if with_intervals:
+        st.set_intervals([tuple(iv) for iv in g["intervals"]])
+    return st
+
+
+def _region_candidates_config(v, **kw):
+    # (emit_zero_coverage_refs: "1 when an interval set is supplied", include/pisces_hip.h — RegionState.cs:446)
+    return _abi.default_config(include_reference_calls=1 if v["with_reference"] else 0, emit_zero_coverage_refs=1 if v["with_intervals"] else 0, **kw)
+
+
+_REGION_CANDIDATES = load("region_candidates.json")
+
+
+@pytest.mark.parametrize("v", _REGION_CANDIDATES["variants"], ids=lambda v: v["name"])
+def test_get_all_candidates_reference_cases(v):
+    """RegionStateTests.ExecuteTest_GetCandidates (:339-437), all four of :258-279: the list GetAllCandidates returns — the candidates as
+    added (the SNV at 15 too, outside the intervals: intervals limit Reference candidates only), a Reference candidate with the reference
+    base's support by direction where there is coverage, and inside an interval set also where there is none."""
+    g = _REGION_CANDIDATES
+    st = _region_candidates_state(g, v["with_intervals"])
+    got = st.all_candidates(g["reference"], _region_candidates_config(v))
+    key = lambda c: (c["pos"], c["category"], c["ref"], c["alt"], tuple(c["support"]))
+    assert sorted((c.position, c.category, c.ref.decode(), c.alt.decode(), tuple(c.support_by_dir)) for c in got) == \
+        sorted((c["pos"], _CAT[c["category"]], c["ref"], c["alt"], tuple(c["support"])) for c in v["expect"])
+
+
+_CALLER_MNV = load("caller_mnv_cases.json")
+
+
+def caller_mnv_config(sc, **kw):
+    c = sc["config"]
+    freq = float(np.float32(c["min_frequency_num"]) / np.float32(c["min_frequency_den"])) if "min_frequency_num" in c else c["min_frequency"]
+    return _abi.default_config(rmxn_max_repeat_length=-1, variant_qscore_filter=-1, low_depth_filter=-1, variant_freq_filter=-1.0, no_call_filter_threshold=-1.0,
+                               max_variant_qscore=c["max_variant_qscore"], noise_level=c["noise_level"], min_coverage=c["min_coverage"],
+                               min_variant_qscore=c["min_variant_qscore"], include_reference_calls=c["include_reference_calls"], min_frequency=freq,
+                               call_mnvs=1, collapse=0, max_mnv_length=8, **kw)
+
+
+def caller_mnv_multiplier(sc, position):
+    m = _CALLER_MNV["multipliers"]
+    return m["high"] if position == sc["high_coverage_coordinate"] else m["low"] if position == sc["low_coverage_coordinate"] else m["normal"]
+
+
+@pytest.mark.parametrize("sc", _CALLER_MNV["scenarios"], ids=lambda s: s["name"])
+def test_allele_caller_mnv_reallocation_cases(sc):
+    """VariantCallerTests.CallVariants_MnvReallocation / _MnvTakingRefSupport / _MnvReallocatesToDifferentBlock /
+    _MnvReallocatesToSnvOutsideInterval (:307-656): MNV reallocation as AlleleCaller.Call drives it — who gains the failed MNVs' support,
+    what is handed to the next block past MaxClearedPosition, the reference support a gapped MNV takes, and the interval set applied to
+    what reallocation makes."""
+    lo, hi = sc["positions_touched"]
+    st = orc.State(1, 2100)
+    for p in range(lo, hi + 1):
+        for a in range(6):
+            for d in range(3):
+                st.set_count(p, a, d, 5, caller_mnv_multiplier(sc, p))
+    if sc["intervals"]:
+        st.set_intervals([tuple(iv) for iv in sc["intervals"]])
+    cands = [orc.make_candidate(c["pos"], _CAT[c["category"]], c["ref"], c["alt"], support=tuple(c["support"])) for c in sc["candidates"]]
+    _, full, _ = orc.call_candidates(st, cands, caller_mnv_config(sc), max_cleared_position=sc["max_cleared_position"])
+    same = lambda f, e: (f.position, f.category, f.ref.decode(), f.alt.decode()) == (e["pos"], _CAT[e["category"]], e["ref"], e["alt"])
+    for e in sc["expect_called"]:
+        rows = [f for f in full if same(f, e)]
+        assert len(rows) == 1, e
+        for field in ("allele_support", "total_coverage", "reference_support"):
+            if field in e:
+                assert getattr(rows[0], field) == e[field], (e, field)
+        if "frequency" in e:   # CalledAllele.Frequency, float: AlleleSupport / TotalCoverage
+            assert np.float32(rows[0].allele_support) / np.float32(rows[0].total_coverage) == np.float32(e["frequency"])
+    for e in sc["expect_absent"]:
+        assert not [f for f in full if same(f, e)], e
+    for e in sc["expect_no_reference_row"]:
+        for f in full:
+            if f.position == e["pos"] and f.category == _abi.CAT_REFERENCE:
+                assert "allele_support" in e or "allele_support_above" in e, e
+                assert f.allele_support != e.get("allele_support") and not f.allele_support > e.get("allele_support_above", 1 << 30), e
+    if "expect_called_count" in sc:
+        assert len(full) == sc["expect_called_count"], [(f.position, f.ref, f.alt) for f in full]
+    if "expect_gapped_mnv_ref" in sc:   # what AddGappedMnvRefCount was given: these and nothing else
+        want = dict(map(tuple, sc["expect_gapped_mnv_ref"]))
+        assert {p: st.get_gapped_mnv_ref(p) for p in range(1, 2101) if st.get_gapped_mnv_ref(p)} == want
+    # IAlleleSource.AddCandidates: the batch was an explicit list, so what the state holds now is what the call handed to the next block
+    handed = sorted((c.position, c.category, c.ref.decode(), c.alt.decode(), tuple(c.support_by_dir)) for c in st.candidates())
+    assert handed == sorted((c["pos"], _CAT[c["category"]], c["ref"], c["alt"], tuple(c["support"])) for c in sc.get("expect_handed_to_next_block", []))
+
+
+def test_ref_support_taken_by_gapped_mnvs():
+    """VariantCallerTests.GetRefSupportFromGappedMnvs (:658-763): the eight alleles as one callable batch (nothing fails: no thresholds);
+    the map AlleleCaller registers with the state is {13: 15, 124: 36, 78901: 25, 78903: 25} and has none of the keys the test asserts
+    absent — nor any other."""
+    g = load("gapped_mnv_ref_support.json")
+    st = orc.State(1, g["reference_length"])
+    cands = [orc.make_candidate(a["pos"], _CAT[a["category"]], a["ref"], a["alt"], support=(a["allele_support"], 0, 0)) for a in g["alleles"]]
+    cfg = _abi.default_config(rmxn_max_repeat_length=-1, variant_qscore_filter=-1, low_depth_filter=-1, variant_freq_filter=-1.0, no_call_filter_threshold=-1.0,
+                              min_coverage=0, min_variant_qscore=0, min_frequency=0.0, call_mnvs=1, collapse=0, max_mnv_length=8)
+    _, full, _ = orc.call_candidates(st, cands, cfg)
+    assert len(full) == len(g["alleles"])
+    for p in g["expect_absent"]:
+        assert st.get_gapped_mnv_ref(p) == 0, p
+    gapped = np.array([st.get_gapped_mnv_ref(p) for p in range(1, g["reference_length"] + 1)])
+    assert {int(i) + 1: int(gapped[i]) for i in np.nonzero(gapped)[0]} == dict(map(tuple, g["expect"]))

@@ -14,6 +14,12 @@ tests/golden/ (transcribed from the reference's tests, file:line in each), and t
       collapser_cases.json         VariantCollapserTests.cs:18-204, 869-1033  -> the flush's collapser, frequencies from the device's counts
       coverage_spanning.json       CoverageCalculatorTests.cs:69-702          -> the candidate kernel's coverage / the tile kernels' point coverage
       caller_matrix.json           VariantCallerTests.cs:27-277               -> IsCallable by coverage / frequency / q-score, reference pruning
+      done_processing.json         RegionStateManagerTests.cs:707-781         -> the flush's block choice and DoneProcessing: a cleared block's counts read 0, held blocks keep theirs
+      gapped_mnv_ref.json          RegionStateManagerTests.cs:136-169; RegionStateTests.cs:282-325 -> pisces_hip_add_gapped_mnv_ref / pisces_hip_get_gapped_mnv_ref
+      region_candidates.json       RegionStateTests.cs:339-437                -> the rows of GetAllCandidates' candidates: Reference rows by coverage and interval set
+      caller_mnv_cases.json        VariantCallerTests.cs:307-656              -> MNV reallocation as the flush drives it: block edge, interval edge, reference support taken
+      gapped_mnv_ref_support.json  VariantCallerTests.cs:658-763              -> the reference support the gaps of a flush's MNVs take from its Reference rows
+    (region_state.json's `deletions`, RegionStateManagerTests.cs:597-704, is read input: tests/test_gpu_parity.py beside the other read scenarios)
 """
 import ctypes as C
 import json
@@ -27,6 +33,7 @@ from pisces_amd import _abi
 G = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 load = lambda name: json.load(open(os.path.join(G, name)))
 ALLELE = {"A": 0, "G": 1, "C": 2, "T": 3, "N": 4, "Deletion": 5, "Del": 5}
+DIR = {"F": 0, "R": 1, "S": 2}
 CAT = {"Snv": _abi.CAT_SNV, "Insertion": _abi.CAT_INSERTION, "Deletion": _abi.CAT_DELETION, "Mnv": _abi.CAT_MNV, "Reference": _abi.CAT_REFERENCE}
 GT_CODE = {"HeterozygousAlt1Alt2": 0, "Alt12LikeNoCall": 1, "HeterozygousAltRef": 2, "HomozygousAlt": 3, "HomozygousRef": 4,
            "RefLikeNoCall": 5, "AltLikeNoCall": 6, "RefAndNoCall": 7, "AltAndNoCall": 8}
@@ -401,3 +408,259 @@ def test_product_allele_caller_matrix(torch_cuda, sc):
         x = _MATRIX["candidates"][name]
         want.append((x["chr"], x["pos"], x["ref"], x["alt"], CAT[x["category"]], None if x["category"] == "Reference" else sum(x["support"])))
     assert sorted(got, key=str) == sorted(want, key=str)
+
+
+# ---- region state, caller and MNV paths: the tables tests/test_oracle_golden.py pins the oracle with, through the library -----------
+_DONE = load("done_processing.json")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("placement", ["default", "every batch its own segment"])
+@pytest.mark.parametrize("flush", ["copying flush", "CallBegin + CallEnd"])
+def test_product_done_processing_reference_case(torch_cuda, flush, placement):
+    """RegionStateManagerTests.DoneProcessing (:707-781) through the library: six 1-base reads in six blocks, an SNV candidate and a
+    deletion whose 3500-base reference allele reaches from block 3001-4000 to 6501, one flush per upTo of the test and after each the
+    GetAlleleCount values it asserts.  A flushed block's counts read 0 (the read store calls its floor "not a compaction": what it
+    serves for a cleared block is checked here), block 3001-4000 keeps its count while the deletion reaches past upTo and block
+    5001-6000 keeps its count behind it.  With copying flushes and with the CallBegin / CallEnd pair, in both placements of the store."""
+    from pisces_amd import engine
+    from tests.test_read_store import STORE_MODES, env
+    g = _DONE
+    ref = bytearray(b"A" * 8100)
+    ref[0] = ord("T")
+    cfg = _abi.default_config(block_size=g["block_size"], rmxn_max_repeat_length=-1)
+    cands = []
+    for x in g["candidates"]:
+        ref_allele = x["ref_base"] * x["ref_length"] if "ref_length" in x else x["ref"]
+        cands.append({"position": x["pos"], "category": CAT[x["category"]], "ref": ref_allele, "alt": x["alt"], "support_by_dir": tuple(x["support"])})
+    with env(PISCES_HIP_READ_PATH=None, **STORE_MODES[placement]):
+        with engine.HipVariantCaller(cfg) as c:
+            count = lambda e: [e[0], e[1], e[2], c.GetAlleleCount(e[0], ALLELE[e[1]], DIR[e[2]])]
+            c.SetReference(bytes(ref))
+            c.AddAlleleCounts([{"pos": r["pos"], "seq": r["seq"], "cigar": [("M", len(r["seq"]))], "quals": [r["qual"]] * len(r["seq"])} for r in g["reads"]])
+            assert [count(e) for e in g["expect_before"]] == g["expect_before"]
+            c.AddCandidates(cands)
+            for step in g["steps"]:
+                if flush == "copying flush":
+                    c.Call(step["up_to"])
+                else:
+                    c.CallBegin(step["up_to"])
+                    c.CallEnd()
+                assert [count(e) for e in step["expect"]] == step["expect"], step["up_to"]
+
+
+@pytest.mark.gpu
+def test_product_gapped_mnv_ref_add_and_get(torch_cuda):
+    """RegionStateManagerTests.AddAndGetGappedMnvRefCount (:136-169) and RegionStateTests.AddAndGetGappedMnvReferenceCounts (:282-302)
+    through pisces_hip_add_gapped_mnv_ref / pisces_hip_get_gapped_mnv_ref: counts add up per position, an add of 0 and positions not
+    named change nothing.  The handle is the manager (blocks on demand), so the single RegionState's out-of-region add and get
+    (:305-325) follow what include/pisces_hip.h promises instead: any position > 0 is accepted, a position never named reads 0, a
+    position <= 0 is refused by both entries and a refused add adds nothing of its call."""
+    from pisces_amd import engine
+    g = load("gapped_mnv_ref.json")
+    for steps in (g["manager"]["steps"], g["region"]["steps"]):
+        with engine.HipVariantCaller(_abi.default_config()) as c:
+            for step in steps:
+                c.AddGappedMnvRefCount(dict(map(tuple, step["add"])))
+                assert [[p, c.GetGappedMnvRefCount(p)] for p, _ in step["expect"]] == step["expect"]
+    e = g["region_errors"]
+    with engine.HipVariantCaller(_abi.default_config()) as c:
+        c.AddGappedMnvRefCount(dict(map(tuple, e["add"])))
+        everything = lambda: [c.GetGappedMnvRefCount(p) for p in range(e["start"], e["end"] + 1)]
+        before = everything()
+        nonzero = dict(map(tuple, e["expect_all_after"]["nonzero"]))
+        assert before == [nonzero.get(p, 0) for p in range(e["start"], e["end"] + 1)]
+        outside, n = e["add_outside"]
+        assert c.GetGappedMnvRefCount(outside) == 0 and c.GetGappedMnvRefCount(2 ** 31 - 1) == 0   # never named: 0, however far out
+        c.AddGappedMnvRefCount({outside: n})                  # the manager makes the block: accepted, and nothing else moves
+        assert c.GetGappedMnvRefCount(outside) == n and everything() == before
+        for bad in (0, -5):
+            with pytest.raises(engine.PiscesHipError):
+                c.GetGappedMnvRefCount(bad)
+            with pytest.raises(engine.PiscesHipError):
+                c.AddGappedMnvRefCount({e["start"]: 7, bad: 1})   # refused as a whole: the valid position before it is not added either
+        assert c.GetGappedMnvRefCount(outside) == n and everything() == before
+
+
+_REGION_CANDIDATES = load("region_candidates.json")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("v", _REGION_CANDIDATES["variants"], ids=lambda v: v["name"])
+def test_product_region_candidates_reference_cases(torch_cuda, v):
+    """RegionStateTests.ExecuteTest_GetCandidates (:339-437), all four of :258-279 (with / without Reference candidates = gVCF or not,
+    with / without intervals), through the library.  The library reports rows, not candidates: the expected rows are the golden's
+    candidate list after ShouldReport (AlleleCaller.cs:260-263: inside the intervals when there are any) and after the reference pruning
+    of ComputeGenotypeAndFilterAllele (:146-147: a Reference allele leaves where a variant is called); every threshold is off, so each
+    remaining candidate is one row.  Checked: position, category, support by direction; on Reference rows also AlleleSupport and
+    TotalCoverage; and the whole row set against the oracle's for the same state.
+    Visible on the oracle only (test_get_all_candidates_reference_cases): that the SNV at 15 stays a *candidate* outside the intervals,
+    and the Reference candidates [0, 0, 5] at 5 and [5, 5, 0] at 15, which the SNVs called there prune from the rows.
+    MNV calling on in its earlier form (PISCES_HIP_MNV_SPLIT=0): SNV candidates are the host's, none is made from the counts."""
+    from pisces_amd import engine
+    from tests import orc
+    from tests.test_gpu_parity import assert_records_match
+    from tests.test_read_store import env
+    g = _REGION_CANDIDATES
+    cfg = _permissive(call_mnvs=1, collapse=0, include_reference_calls=1 if v["with_reference"] else 0, emit_zero_coverage_refs=1 if v["with_intervals"] else 0)
+    cells = {(r["pos"], ALLELE[r["allele"]], DIR[r["dir"]], g["anchor_index"]): r["n"] for r in g["counts"]}
+    with env(PISCES_HIP_MNV_SPLIT=0):
+        with engine.HipVariantCaller(cfg) as c:
+            c.SetReference(g["reference"])
+            if v["with_intervals"]:
+                c.SetIntervals([tuple(iv) for iv in g["intervals"]])
+            _stage(c, cells)
+            c.AddCandidates([{"position": x["pos"], "category": CAT[x["category"]], "ref": x["ref"], "alt": x["alt"], "support_by_dir": tuple(x["support"])}
+                             for x in g["candidates"]])
+            recs, alleles = c.CallWithAlleles()
+    inside = lambda p: not v["with_intervals"] or any(a <= p <= b for a, b in g["intervals"])
+    reported = [x for x in v["expect"] if inside(x["pos"])]
+    variant_at = {x["pos"] for x in reported if x["category"] != "Reference"}
+    want = [x for x in reported if x["category"] != "Reference" or x["pos"] not in variant_at]
+    got = sorted((int(r["position"]), _abi.info_category(r["info"]), a[0], a[1], tuple(int(k) for k in r["support_by_dir"])) for r, a in zip(recs, alleles))
+    assert got == sorted((x["pos"], CAT[x["category"]], x["ref"], x["alt"], tuple(x["support"])) for x in want)
+    coverage = {}
+    for r in g["counts"]:
+        coverage[r["pos"]] = coverage.get(r["pos"], 0) + r["n"]
+    for r in recs:
+        if _abi.info_category(r["info"]) == _abi.CAT_REFERENCE:
+            x = [x for x in want if x["pos"] == int(r["position"])][0]
+            assert int(r["allele_support"]) == sum(x["support"]) and int(r["total_coverage"]) == coverage.get(x["pos"], 0), x
+    # the same state through the oracle: every row, field by field
+    st = orc.State(g["region"][0], g["region"][1] - g["region"][0] + 1)
+    for x in g["candidates"]:
+        st.add_candidate(orc.make_candidate(x["pos"], CAT[x["category"]], x["ref"], x["alt"], support=tuple(x["support"])))
+    for (p, a, d, anchor), n in cells.items():
+        st.set_count(p, a, d, anchor, n)
+    if v["with_intervals"]:
+        st.set_intervals([tuple(iv) for iv in g["intervals"]])
+    exp = st.call_all(g["reference"], cfg)
+    assert_records_match(recs, exp)
+
+
+_CALLER_MNV = load("caller_mnv_cases.json")
+
+
+def _caller_mnv_run(sc, candidates, split_env):
+    """One handle for the scenario: the mock state's counts at the positions its candidates span (multiplier x 6 alleles x 3 directions),
+    a reference that agrees with the SNV / MNV candidates' reference alleles (so the gaps of ATCTGTGA over TTTTTTTT are gaps), the
+    candidates, one flush; returns (rows, alleles, candidates the state holds afterwards)."""
+    from pisces_amd import engine
+    from tests.test_oracle_golden import caller_mnv_config, caller_mnv_multiplier
+    from tests.test_read_store import env
+    lo, hi = sc["positions_touched"]
+    ref = bytearray(b"A" * 2100)
+    for want_point_alleles in (False, True):   # (a deletion's reference allele first: where the two disagree, the MNV's is the reference)
+        for x in sc["candidates"]:
+            if (x["category"] in ("Snv", "Mnv")) == want_point_alleles:
+                ref[x["pos"] - 1:x["pos"] - 1 + len(x["ref"])] = x["ref"].encode()
+    cells = {(p, a, d, 5): caller_mnv_multiplier(sc, p) for p in range(lo, hi + 1) for a in range(6) for d in range(3)}
+    # MaxClearedPosition 2000 with candidates that reach 2002: the batch GetCandidatesToProcess makes for an upTo in block 2001-3000 that
+    # is not below those candidates' ends (RegionStateManager.cs:295-320; at upTo = 2000 block 1001-2000 is held by its own MNVs, :306)
+    up_to = None if sc["max_cleared_position"] is None or hi <= sc["max_cleared_position"] else hi
+    with env(PISCES_HIP_MNV_SPLIT=split_env):
+        with engine.HipVariantCaller(caller_mnv_config(sc, block_size=1000)) as c:
+            c.SetReference(bytes(ref))
+            if sc["intervals"]:
+                c.SetIntervals([tuple(iv) for iv in sc["intervals"]])
+            _stage(c, cells)
+            c.AddCandidates([{"position": x["pos"], "category": CAT[x["category"]], "ref": x["ref"], "alt": x["alt"], "support_by_dir": tuple(x["support"])}
+                             for x in candidates])
+            recs, alleles = c.CallWithAlleles(up_to)
+            held = c.GetCandidates()
+    return recs, alleles, held
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("form", ["split", "PISCES_HIP_MNV_SPLIT=0"])
+@pytest.mark.parametrize("sc", _CALLER_MNV["scenarios"], ids=lambda s: s["name"])
+def test_product_allele_caller_mnv_reallocation_cases(torch_cuda, sc, form):
+    """VariantCallerTests.CallVariants_MnvReallocation / _MnvTakingRefSupport / _MnvReallocatesToDifferentBlock /
+    _MnvReallocatesToSnvOutsideInterval (:307-656) through the library's flush, in both forms of MNV calling: who gains the failed MNVs'
+    support, the failed MNVs gone, no Reference row with the support the test rules out, ReferenceSupport 290 on the SNV under the
+    gapped MNV and nothing taken anywhere else, the passing deletion as it is without the MNV, exactly the three candidates handed to
+    block 2001-3000 (GetCandidates after the flush: category, position, alleles, support), exactly two called alleles at the interval edge.
+    The tests' batches hold no Reference candidates; here a gVCF scenario also has the Reference rows of the staged positions."""
+    from tests.test_oracle_golden import caller_mnv_multiplier
+    split_env = None if form == "split" else 0
+    recs, alleles, held = _caller_mnv_run(sc, sc["candidates"], split_env)
+    rows = [(int(r["position"]), _abi.info_category(r["info"]), a[0], a[1], r) for r, a in zip(recs, alleles)]
+    listing = [x[:4] + (int(x[4]["allele_support"]),) for x in rows]
+    same = lambda x, e: x[:4] == (e["pos"], CAT[e["category"]], e["ref"], e["alt"])
+    for e in sc["expect_called"]:
+        hit = [x[4] for x in rows if same(x, e)]
+        assert len(hit) == 1, (e, listing)
+        for field in ("allele_support", "total_coverage", "reference_support"):
+            if field in e:
+                assert int(hit[0][field]) == e[field], (e, field, listing)
+        if "frequency" in e:
+            assert np.float32(hit[0]["allele_support"]) / np.float32(hit[0]["total_coverage"]) == np.float32(e["frequency"])
+    for e in sc["expect_absent"]:
+        assert not [x for x in rows if same(x, e)], (e, listing)
+    for e in sc["expect_no_reference_row"]:
+        for x in rows:
+            if x[0] == e["pos"] and x[1] == _abi.CAT_REFERENCE:
+                assert "allele_support" in e or "allele_support_above" in e, (e, listing)
+                assert int(x[4]["allele_support"]) != e.get("allele_support") and not int(x[4]["allele_support"]) > e.get("allele_support_above", 1 << 30), (e, listing)
+    if "expect_called_count" in sc:
+        assert len([x for x in rows if x[1] != _abi.CAT_REFERENCE]) == sc["expect_called_count"], listing
+    if "expect_gapped_mnv_ref" in sc:
+        taken = dict(map(tuple, sc["expect_gapped_mnv_ref"]))
+        # "the lookup holds 306 and nothing else": a Reference row of another position has all three directions of its base
+        refs = [x for x in rows if x[1] == _abi.CAT_REFERENCE and x[0] not in taken]
+        assert refs, listing
+        for x in refs:
+            assert int(x[4]["allele_support"]) == 3 * caller_mnv_multiplier(sc, x[0]), listing
+        # the passing deletion: the row it has when the gapped MNV is not there at all
+        alone = _caller_mnv_run(sc, [x for x in sc["candidates"] if x["category"] != "Mnv"], split_env)
+        deletion = lambda rs, als: [r for r, a in zip(rs, als) if _abi.info_category(r["info"]) == _abi.CAT_DELETION]
+        (with_mnv,), (without,) = deletion(recs, alleles), deletion(alone[0], alone[1])
+        for field in ("allele_support", "total_coverage", "reference_support", "coverage_by_dir"):
+            assert (with_mnv[field] == without[field]).all(), field
+    got_held = sorted((x["position"], x["category"], x["ref"], x["alt"], tuple(x["support_by_dir"])) for x in held)
+    assert got_held == sorted((x["pos"], CAT[x["category"]], x["ref"], x["alt"], tuple(x["support"])) for x in sc.get("expect_handed_to_next_block", []))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("form", ["split", "PISCES_HIP_MNV_SPLIT=0"])
+def test_product_ref_support_taken_by_gapped_mnvs(torch_cuda, form):
+    """VariantCallerTests.GetRefSupportFromGappedMnvs (:658-763) through a gVCF flush over the eight alleles as candidates (no threshold:
+    all are callable), counts staged at the asserted positions only — the reference base, (40, 30, 30) by direction.  The Reference rows
+    at 13, 124, 78901 and 78903 lose exactly 15, 36, 25 and 25.  At a position the test asserts absent nothing is lost: its Reference
+    row has the staged 100 — it must be there where no candidate starts (14, 125, 457, 458, 78902, 78904); where an MNV, a deletion or
+    an insertion is called the Reference allele is pruned (AlleleCaller.cs:146-147) and there is nothing to lose; at 93000 the SNV row's
+    ReferenceSupport is the staged 100."""
+    from pisces_amd import engine
+    from tests.test_read_store import env
+    g = load("gapped_mnv_ref_support.json")
+    ref = bytearray(b"A" * g["reference_length"])
+    for a in g["alleles"]:
+        ref[a["pos"] - 1:a["pos"] - 1 + len(a["ref"])] = a["ref"].encode()
+    staged = (40, 30, 30)
+    taken = dict(map(tuple, g["expect"]))
+    cells = {(p, ALLELE[chr(ref[p - 1])], d, 5): staged[d] for p in list(taken) + g["expect_absent"] for d in range(3)}
+    cfg = _permissive(call_mnvs=1, collapse=0, include_reference_calls=1, max_mnv_length=8)
+    with env(PISCES_HIP_MNV_SPLIT=None if form == "split" else 0):
+        with engine.HipVariantCaller(cfg) as c:
+            c.SetReference(bytes(ref))
+            _stage(c, cells)
+            c.AddCandidates([{"position": a["pos"], "category": CAT[a["category"]], "ref": a["ref"], "alt": a["alt"], "support_by_dir": (a["allele_support"], 0, 0)}
+                             for a in g["alleles"]])
+            recs, alleles = c.CallWithAlleles()
+    listing = [(int(r["position"]), _abi.info_category(r["info"]), a, int(r["allele_support"])) for r, a in zip(recs, alleles)]
+    for a in g["alleles"]:   # every allele is called as it was handed in
+        assert (a["pos"], CAT[a["category"]], (a["ref"], a["alt"]), a["allele_support"]) in listing, (a, listing)
+    reference_rows = {}
+    for r in recs:
+        if _abi.info_category(r["info"]) == _abi.CAT_REFERENCE:
+            assert int(r["position"]) not in reference_rows
+            reference_rows[int(r["position"])] = int(r["allele_support"])
+    starts = {a["pos"] for a in g["alleles"]}
+    assert {p: reference_rows.get(p) for p in taken} == {p: sum(staged) - n for p, n in taken.items()}, listing
+    for p in g["expect_absent"]:
+        if p not in starts:
+            assert reference_rows.get(p) == sum(staged), (p, listing)
+        else:
+            assert reference_rows.get(p, sum(staged)) == sum(staged), (p, listing)
+    (snv,) = [r for r in recs if _abi.info_category(r["info"]) == _abi.CAT_SNV]
+    assert int(snv["position"]) == 93000 and int(snv["reference_support"]) == sum(staged)
