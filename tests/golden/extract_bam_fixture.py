@@ -21,7 +21,7 @@ import numpy as np
 
 OFFSET = 3118000
 WINDOW = (3118001, 3119000)
-CIGAR_OPS = "MIDNSHP=X"
+CIGAR_OPS = "MIDNSHP=X" + "?" * 7   # (op codes 9-15 are reserved)
 SEQ_CODE = "=ACMGRSVTWYHKDBN"
 
 
