@@ -234,6 +234,10 @@ namespace Pisces.Hip
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pisces_hip_add_reads_amplicons(IntPtr handle, ref PiscesReadBatch batch, int[] ampliconId);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pisces_hip_add_device_reads_amplicons(IntPtr handle, ref PiscesReadBatch deviceBatch, long nCigarOps, long nBases, IntPtr deviceAmpliconId);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pisces_hip_get_amplicon_counts(IntPtr handle, int startPosition, int n, [Out] int[] ids, [Out] int[] coverage, [Out] int[] support);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pisces_hip_bam_fetch_amplicons(IntPtr handle, [Out] int[] ampliconId);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pisces_hip_amplicon_name_count(IntPtr handle);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pisces_hip_get_amplicon_name(IntPtr handle, int id, [Out] byte[] name, int capacity);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pisces_hip_intern_amplicon_name(IntPtr handle, byte[] name, int length);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pisces_hip_amplicon_bias(int[] support, int[] coverage, int n, float threshold, [Out] double[] chanceOut);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pisces_hip_vcf_default_config(out PiscesVcfConfig cfg);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern long pisces_hip_format_vcf(ref PiscesVcfConfig cfg, [MarshalAs(UnmanagedType.LPStr)] string chrom, PiscesCalledAllele[] records, long n, int[] candIndex, PiscesCandidate[] cands, byte[] alleles, [Out] byte[] text, long capacity);

@@ -694,11 +694,12 @@ int32_t pisces_hip_amplicon_bias(const int32_t* support, const int32_t* coverage
  * filter_bits (AlleleProcessor.ApplyFilters, AlleleProcessor.cs:45-63) — nothing else of the row changes, rows of other categories never get
  * it (AmpliconBiasCalculator.cs:27).  threshold < 0 = null: off, the default; a handle that is off launches nothing for it.  Must come before
  * the first read is added (PISCES_E_STATE afterwards).  A read's amplicon (Read.GetAmpliconNameIfExists: the BAM XN tag, Read.cs:483-486)
- * crosses as an int32 id the host chooses, -1 = no tag.  PISCES_E_UNSUPPORTED, each with a message, for what cannot go together with
+ * crosses as an int32 id, -1 = no tag: an id the host chooses (pisces_hip_add_reads_amplicons), or an id of the handle's name dictionary,
+ * which pisces_hip_bam_decode fills from the XN tags on the device (below).  PISCES_E_UNSUPPORTED, each with a message, for what cannot go together with
  * tracking: call_mnvs, collapse thresholds that take SNV candidates from the read walk (collapse_freq_threshold > 0 or
  * collapse_freq_ratio_threshold >= 1), forced alleles (set before: the setter refuses; pisces_hip_set_forced_alleles refuses afterwards),
- * PISCES_HIP_READ_PATH=log; and on a tracking handle pisces_hip_add_decoded_reads (the XN tag is not decoded on the device yet) and
- * pisces_hip_add_observations (tuples have no read identity).  The tuple surface (pisces_hip_call_tiles*) never had tags and is untouched.
+ * PISCES_HIP_READ_PATH=log; and on a tracking handle pisces_hip_add_observations (tuples have no read identity) and
+ * pisces_hip_add_decoded_reads when the decoded batch carries no ids (nothing decoded, or decoded before tracking was switched on).  The tuple surface (pisces_hip_call_tiles*) never had tags and is untouched.
  * A flush that meets a position with more than six amplicons (Constants.MaxNumOverlappingAmplicons, Constants.cs:54-62: the reference
  * indexes slot -1 and throws IndexOutOfRangeException) returns PISCES_E_INVALID_ARG naming the lowest such position; the blocks stay held.
  * A flush counts only in the 64-locus tiles that hold a called SNV row with support (the others cannot get the filter and are skipped), so
@@ -814,7 +815,8 @@ int32_t pisces_hip_bgzf_inflate(PiscesHip* h, const uint8_t* file, int64_t n_byt
  * pisces_hip_add_reads takes from a host pass over the CIGARs (log slots, candidate-record slots, the blocks every read touches, the
  * reads it refuses: position <= 0, a CIGAR longer than the read, a read past 2^31 - 1 or far past the end of its reference sequence)
  * the decode has made where the reads are (the blocks as a bit map that came back with `counts`); the call enqueues the read walk and
- * the candidate discovery and returns without waiting. */
+ * the candidate discovery and returns without waiting.  On a handle that tracks amplicon counts the batch must carry amplicon ids (below:
+ * decoded after pisces_hip_set_amplicon_bias_filter), PISCES_E_UNSUPPORTED otherwise; the ids join the read store with the reads. */
 int32_t pisces_hip_bam_decode(PiscesHip* h, const uint8_t* file, int64_t n_bytes, const PiscesBgzfBlock* blocks, int64_t n_blocks, int32_t ref_id,
                               int32_t min_map_quality, int32_t skip_duplicates, int32_t only_proper_pairs, int64_t counts[4]);
 int32_t pisces_hip_bam_fetch(PiscesHip* h, int32_t* position, uint8_t* flags, int32_t* cigar_offset, uint8_t* cigar_op, uint32_t* cigar_len,
@@ -828,6 +830,29 @@ int32_t pisces_hip_bam_chain_mode(PiscesHip* h);
  * host (either pointer may be NULL): returns 1 when the batch has them, 0 when no read of it was stitched, < 0 on error.  A malformed tag
  * (CigarDirection's "Unexpected format in direction string") makes pisces_hip_add_decoded_reads refuse the batch. */
 int32_t pisces_hip_bam_fetch_directions(PiscesHip* h, uint8_t* directions, uint8_t* deletion_directions);
+/* Amplicon names (Read.GetAmpliconNameIfExists: the XN tag, Read.cs:483-486; TagUtils.GetStringTag, BamCommon.cs:1182-1216).  On a handle
+ * that tracks amplicon counts (pisces_hip_set_amplicon_bias_filter) pisces_hip_bam_decode also reads the XN tag of every kept record where
+ * the records are: the FIRST field with the key XN decides; its type byte is upper-cased; Z / H give the bytes up to the NUL, A / C (so
+ * also a / c) a one-byte name; no such field = no amplicon (-1: the read counts under none); an empty string is a name like any other;
+ * names are equal when their bytes are.  An XN field of another type (GetStringTag throws InvalidDataException) lets the decode succeed
+ * and makes pisces_hip_add_decoded_reads refuse the batch with PISCES_E_INVALID_ARG, naming the lowest such read.  Deviation: B arrays in
+ * front of the tag are skipped as the SAM specification says; the reference's walk throws on them.
+ * The distinct names of the batch are interned on the device; only they come to the host, where the handle keeps a dictionary name <-> id:
+ * a name the handle knows keeps its id, new names get the next ids (from 0) in the order of the first kept read that carries each, decodes
+ * in call order — the same files in the same order give the same ids on every run.  A decode that is never added still leaves its names in
+ * the dictionary (harmless: ids only number names).  A handle that does not track reads no tag, launches nothing for it and has no ids.
+ * pisces_hip_bam_fetch_amplicons: the decoded batch's ids (amplicon_id[reads kept]) to the host; returns 1 when the batch has ids, 0 when
+ * it has none, PISCES_E_STATE without a batch or once it has moved into the store (the rules of pisces_hip_bam_fetch_directions).
+ * pisces_hip_amplicon_name_count / pisces_hip_get_amplicon_name: the dictionary; the name's length is returned and its bytes (no
+ * terminator) written only when capacity holds them all; PISCES_E_INVALID_ARG for an id the dictionary does not have.
+ * pisces_hip_intern_amplicon_name: the id of name[0, length) in the same dictionary, a new one when it is new — for a host that parses
+ * some reads itself and feeds pisces_hip_add_reads_amplicons beside the decode; PISCES_E_STATE on a handle that does not track.
+ * Ids a caller invents and ids of the dictionary must not be mixed on one handle: both count from small numbers, and an invented id that
+ * equals a dictionary id is the same amplicon to every count. */
+int32_t pisces_hip_bam_fetch_amplicons(PiscesHip* h, int32_t* amplicon_id);
+int32_t pisces_hip_amplicon_name_count(PiscesHip* h);
+int32_t pisces_hip_get_amplicon_name(PiscesHip* h, int32_t id, char* out, int32_t capacity);
+int32_t pisces_hip_intern_amplicon_name(PiscesHip* h, const char* name, int32_t length);
 
 #ifdef __cplusplus
 }

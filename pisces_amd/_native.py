@@ -26,7 +26,8 @@ EXPORTS = [
     "pisces_hip_adaptive_default_params", "pisces_hip_set_adaptive_params", "pisces_hip_get_posteriors", "pisces_hip_posteriors_view", "pisces_hip_set_posteriors_buffer",
     "pisces_hip_compact_posteriors", "pisces_hip_set_genotypes_adaptive", "pisces_hip_adaptive_genotype_qscore", "pisces_hip_format_vcf_ex", "pisces_hip_format_vcf_padded_ex",
     "pisces_hip_amplicon_bias", "pisces_hip_set_amplicon_bias_filter", "pisces_hip_add_reads_amplicons", "pisces_hip_add_device_reads_amplicons",
-    "pisces_hip_get_amplicon_counts",
+    "pisces_hip_get_amplicon_counts", "pisces_hip_bam_fetch_amplicons", "pisces_hip_amplicon_name_count", "pisces_hip_get_amplicon_name",
+    "pisces_hip_intern_amplicon_name",
 ]
 
 
@@ -123,6 +124,10 @@ def _load():
         "pisces_hip_host_time": (i32, [vp, P(C.c_double), i32]),
         "pisces_hip_set_owned_range": (i32, [vp, i32, i32]),
         "pisces_hip_bam_fetch_directions": (i32, [vp, vp, vp]),
+        "pisces_hip_bam_fetch_amplicons": (i32, [vp, vp]),
+        "pisces_hip_amplicon_name_count": (i32, [vp]),
+        "pisces_hip_get_amplicon_name": (i32, [vp, i32, vp, i32]),
+        "pisces_hip_intern_amplicon_name": (i32, [vp, C.c_char_p, i32]),
         "pisces_hip_call_tiles_graph_build": (i32, [vp, P(_abi.PiscesTileBatch), i32, P(i32)]),
         "pisces_hip_call_tiles_graph_launch": (i32, [vp, i32, vp]),
         "pisces_hip_mark": (i32, [vp, i32, vp]),

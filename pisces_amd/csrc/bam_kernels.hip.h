@@ -24,6 +24,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "bam_amplicon_kernels.hip.h"   // amp_tag_of, kAmpNoTag
 #include "finder_kernels.hip.h"   // kFoundInline
 
 namespace pisces {
@@ -280,6 +281,52 @@ __device__ inline const uint8_t* bam_find_string_tag(const uint8_t* p, const uin
     }
     return nullptr;
 }
+// One walk over a record's auxiliary fields [p, end) for the two tags the decode reads: the Stitcher's XD (type 'Z', as
+// bam_find_string_tag finds it) and, when want_xn, the amplicon name XN as TagUtils.GetStringTag reads it (BamCommon.cs:1055-1109,
+// 1182-1216): the FIRST field whose key is XN decides, whatever its type; the type byte is upper-cased; Z / H give the bytes up to
+// the NUL (none is a name too), A / C one byte, any other type is an error of the read (xn_bad).  The walk goes field by field, so the
+// bytes "XN" inside another field's value match nothing.  It skips B arrays as SAM specification 4.2.4 says; the reference's walk throws
+// on a B field in front of the tag it looks for (a deviation that is kept: DESIGN section 3.9).
+struct BamTags { const uint8_t* xd; const uint8_t* xn; int xd_len, xn_len; bool xn_bad; };
+__device__ inline BamTags bam_find_tags(const uint8_t* p, const uint8_t* end, bool want_xd, bool want_xn)
+{
+    BamTags t = {nullptr, nullptr, 0, 0, false};
+    while (p + 3 <= end && (want_xd || want_xn)) {
+        const uint8_t a = p[0], b = p[1];
+        uint8_t ty = p[2];
+        p += 3;
+        if (want_xn && a == 'X' && b == 'N') {
+            want_xn = false;
+            const uint8_t up = (ty >= 'a' && ty <= 'z') ? (uint8_t)(ty - 32) : ty;   // (Char.ToUpper)
+            if (up == 'Z' || up == 'H') {
+                const uint8_t* q = p;
+                while (q < end && *q) q++;
+                t.xn = p; t.xn_len = (int)(q - p);
+                ty = 'H';                                 // (skipped as the string it was read as; never taken for XD)
+            } else if ((up == 'A' || up == 'C') && p < end) {
+                t.xn = p; t.xn_len = 1;
+                ty = 'A';
+            } else t.xn_bad = true;
+        }
+        if (ty == 'Z' || ty == 'H') {
+            const uint8_t* q = p;
+            while (q < end && *q) q++;
+            if (want_xd && a == 'X' && b == 'D' && ty == 'Z') { t.xd = p; t.xd_len = (int)(q - p); want_xd = false; }
+            p = q + 1;
+        } else if (ty == 'A' || ty == 'c' || ty == 'C') p += 1;
+        else if (ty == 's' || ty == 'S') p += 2;
+        else if (ty == 'i' || ty == 'I' || ty == 'f') p += 4;
+        else if (ty == 'B') {
+            if (p + 5 > end) return t;
+            const uint8_t sub = p[0];
+            const long long count = (uint32_t)bam_le32(p + 1);
+            const int size = (sub == 'c' || sub == 'C') ? 1 : (sub == 's' || sub == 'S') ? 2 : 4;
+            if (count * size > end - (p + 5)) return t;
+            p += 5 + count * size;
+        } else return t;   // not a value type: the fields end here
+    }
+    return t;
+}
 __device__ __forceinline__ const uint8_t* bam_aux_of(const uint8_t* rec)   // rec points behind block_size
 {
     const int l_name = rec[8], n_cigar = (int)bam_le16(rec + 12), l_seq = bam_le32(rec + 16);
@@ -458,7 +505,8 @@ __global__ __launch_bounds__(1024) void bam_scan_ll_kernel(long long* __restrict
 // the chunks' scanned sums), one bit per 1000-locus block a read touches (GetBlock for every position that receives a count,
 // RegionStateManager.cs:361-383: the aligned segments, and a gap or terminal deletion when CheckDeletionQuality lets it count), and
 // the first read the host pass would have refused (first_error = read index * 8 + code; codes below).
-enum { kBamReadPositionNotPositive = 1, kBamReadCigarLongerThanRead = 2, kBamReadPastInt32 = 3, kBamReadPastBlockMap = 4, kBamReadBadDirectionTag = 5 };
+enum { kBamReadPositionNotPositive = 1, kBamReadCigarLongerThanRead = 2, kBamReadPastInt32 = 3, kBamReadPastBlockMap = 4, kBamReadBadDirectionTag = 5,
+       kBamReadBadAmpliconTag = 6 /* an XN field that is neither a string nor a character (GetStringTag throws InvalidDataException) */ };
 constexpr int kBamMaxDirectionRuns = 64;   // runs of an XD tag ("3F4S3R": three); a tag with more is refused (kBamReadBadDirectionTag)
 __global__ __launch_bounds__(256) void bam_decode_kernel(const uint8_t* __restrict__ s, int64_t n, const long long* __restrict__ entry, BamFilter F,
                                                         const int32_t* __restrict__ read0, const int32_t* __restrict__ op0,
@@ -472,7 +520,8 @@ __global__ __launch_bounds__(256) void bam_decode_kernel(const uint8_t* __restri
                                                         uint32_t* __restrict__ block_map, long long n_block_bits,
                                                         unsigned long long* __restrict__ first_error,
                                                         uint8_t* __restrict__ dirs /* per base, or nullptr: no read of the batch has an XD tag */,
-                                                        uint8_t* __restrict__ del_dirs /* two per CIGAR operation, or nullptr */)
+                                                        uint8_t* __restrict__ del_dirs /* two per CIGAR operation, or nullptr */,
+                                                        unsigned long long* __restrict__ amp_tag /* per read: where its XN value lies (amp_tag_of), or nullptr: the handle tracks no amplicons */)
 {
     // per wave: the XD tag of the record being decoded as (end in the expanded CIGAR, DirectionType) runs (CigarDirection, CigarDirection.cs:19-41)
     __shared__ int32_t xd_end[4][kBamMaxDirectionRuns];
@@ -549,12 +598,17 @@ __global__ __launch_bounds__(256) void bam_decode_kernel(const uint8_t* __restri
             // ---- stitched reads (Read.SequencedBaseDirectionMap / CigarDirections, Read.cs:340-400, 664-682): the XD tag gives a
             // DirectionType per base of the EXPANDED CIGAR (deleted bases included); without the tag every base has the strand's
             int n_runs = -1;   // -1: no XD tag
-            if (dirs) {
-                wave_lds_sync();   // (the record before this one is done with the runs)
+            if (dirs || amp_tag) {   // (one walk over the auxiliary fields serves both tags)
+                if (dirs) wave_lds_sync();   // (the record before this one is done with the runs)
                 int xd_bad = 0;
                 if (lane == 0) {
-                    int xd_len = 0;
-                    const uint8_t* xd = bam_find_string_tag(ql + l_seq, rec + bam_le32(rec - 4), 'X', 'D', &xd_len);
+                    const BamTags tags = bam_find_tags(ql + l_seq, rec + bam_le32(rec - 4), dirs != nullptr, amp_tag != nullptr);
+                    if (amp_tag) {
+                        amp_tag[r] = tags.xn ? amp_tag_of((int64_t)(tags.xn - s), tags.xn_len) : kAmpNoTag;
+                        if (tags.xn_bad) atomicMin(first_error, (unsigned long long)r * 8ull + (unsigned long long)kBamReadBadAmpliconTag);
+                    }
+                    const uint8_t* const xd = tags.xd;
+                    const int xd_len = tags.xd_len;
                     if (xd) {
                         int runs = 0, num = 0, end = 0, digits = 0;
                         for (int k = 0; k < xd_len && !xd_bad; k++) {
@@ -574,8 +628,10 @@ __global__ __launch_bounds__(256) void bam_decode_kernel(const uint8_t* __restri
                         if (xd_bad) atomicMin(first_error, (unsigned long long)r * 8ull + (unsigned long long)kBamReadBadDirectionTag);
                     }
                 }
-                n_runs = __shfl(n_runs, 0, 64);
-                wave_lds_sync();   // (lane 0's runs are in LDS for the other lanes)
+                if (dirs) {
+                    n_runs = __shfl(n_runs, 0, 64);
+                    wave_lds_sync();   // (lane 0's runs are in LDS for the other lanes)
+                }
             }
             auto direction_at = [&](int expanded_index) -> uint8_t {   // (bases the tag does not reach keep DirectionType's default)
                 for (int j = 0; j < n_runs; j++)

@@ -312,6 +312,10 @@ struct PiscesHip {
     float amp_threshold = -1.0f;
     const int32_t* amp_pending = nullptr;   // the ids (in d_amp_in) of the batch an *_amplicons add is handing to the plain add; nullptr: -1 throughout
     DeviceBuf<int32_t> d_amp_in, d_amp_words, d_amp_table;
+    // amplicon names <-> ids: filled by the decodes of a tracking handle (first appearance in file order, decodes in call order) and by
+    // pisces_hip_intern_amplicon_name; a name keeps its id for the handle's life
+    std::vector<std::string> amp_names;
+    std::unordered_map<std::string, int32_t> amp_name_id;
     DeviceBuf<PiscesTile> d_tiles_x;
     DeviceBuf<PiscesTileResult> d_tr_x;
     DeviceBuf<PiscesCalledAllele> d_rec_x;
@@ -547,6 +551,14 @@ struct PiscesHip {
         bool added = false;       // pisces_hip_add_decoded_reads took the batch (moved or copied): it is not added twice
         int32_t chain_mode = 0;   // 0: every chunk's entry guessed and checked; 1: the serial hop ran
         int32_t min_bq = 0;
+        // a tracking handle (pisces_hip_set_amplicon_bias_filter): the XN tag of every read of the batch as an id of the handle's dictionary
+        // (bam_amplicon_kernels.hip.h)
+        bool has_amp = false;     // amp_ids holds an id per read of the batch (the decode ran on a tracking handle)
+        DeviceBuf<unsigned long long> amp_tag, amp_table, amp_words;
+        DeviceBuf<int32_t> amp_slot, amp_slot_first, amp_slot_id, amp_ids;
+        DeviceBuf<AmpliconName> amp_names;
+        DeviceBuf<uint8_t> amp_name_bytes;
+        DeviceBuf<uint32_t> amp_counters;
     } bam;
 
     // the read store (store_kernels.hip.h): the reads of the blocks not yet flushed stay in HBM as they came, a flush calls from them

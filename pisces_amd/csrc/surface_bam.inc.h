@@ -132,6 +132,85 @@ int32_t pisces_hip_bgzf_inflate(PiscesHip* h, const uint8_t* file, int64_t n_byt
     });
 }
 
+// ---- the XN tags of a decoded batch -> ids of the handle's dictionary (bam_amplicon_kernels.hip.h) ------------------------
+// The id of a name, a new one when the handle has not met it: ids count from 0 in the order the names arrive.
+static int32_t amplicon_name_id(PiscesHip* h, const std::string& name)
+{
+    auto it = h->amp_name_id.find(name);
+    if (it != h->amp_name_id.end()) return it->second;
+    const int32_t id = (int32_t)h->amp_names.size();
+    h->amp_names.push_back(name);
+    h->amp_name_id.emplace(name, id);
+    return id;
+}
+
+// B.amp_tag (the decode kernel's) -> B.amp_ids.  The table starts at kAmpTableSlots and is rerun four times larger while more than half
+// of it is taken, up to the power of two above twice the batch's reads (where it cannot be more than half full): a handful of passes,
+// and nothing of an abandoned pass is used.  Only the distinct names come to the host; they join the dictionary in the order of the
+// first read that carries each (file order), which no race on the device can change.
+static int32_t bam_intern_amplicons(PiscesHip* h)
+{
+    auto& B = h->bam;
+    const int32_t nr = (int32_t)B.n_reads;
+    PISCES_HIP_CHECK(h, B.amp_ids.reserve((size_t)nr + 1));
+    if (nr == 0) { B.has_amp = true; return PISCES_OK; }
+    size_t limit = kAmpTableSlots;
+    while (limit < 2 * (size_t)nr) limit <<= 1;
+    PISCES_HIP_CHECK(h, B.amp_slot.reserve((size_t)nr));
+    PISCES_HIP_CHECK(h, B.amp_words.reserve(4));
+    PISCES_HIP_CHECK(h, B.amp_counters.reserve(2));
+    const unsigned grid = (unsigned)((nr + 255) / 256);
+    unsigned long long words[3] = {0, 0, 0};
+    size_t slots = kAmpTableSlots;
+    for (;;) {
+        PISCES_HIP_CHECK(h, B.amp_table.reserve(slots));
+        PISCES_HIP_CHECK(h, B.amp_slot_first.reserve(slots));
+        PISCES_HIP_CHECK(h, hipMemsetAsync(B.amp_table.p, 0xFF, slots * sizeof(unsigned long long), h->stream));
+        PISCES_HIP_CHECK(h, hipMemsetD32Async((hipDeviceptr_t)B.amp_slot_first.p, kAmpNoRead, slots, h->stream));
+        PISCES_HIP_CHECK(h, hipMemsetAsync(B.amp_words.p, 0, 3 * sizeof(unsigned long long), h->stream));
+        hipLaunchKernelGGL(amplicon_intern_kernel, dim3(grid), dim3(256), 0, h->stream, (const uint8_t*)B.d_stream.p, (const unsigned long long*)B.amp_tag.p, nr,
+                           B.amp_table.p, B.amp_slot_first.p, (uint32_t)(slots - 1), B.amp_slot.p, B.amp_words.p);
+        PISCES_HIP_CHECK(h, hipGetLastError());
+        PISCES_HIP_CHECK(h, hipMemcpyAsync(words, B.amp_words.p, sizeof(words), hipMemcpyDeviceToHost, h->stream));
+        PISCES_HIP_CHECK(h, hipStreamSynchronize(h->stream));
+        if (words[0] * 2 <= slots && words[2] == 0) break;
+        if (slots >= limit) return fail(h, PISCES_E_DEVICE, "bam_decode: the amplicon name table did not settle");   // (cannot be: at most nr names)
+        slots = std::min(slots * 4, limit);
+    }
+    const size_t n_names = (size_t)words[0], n_bytes = (size_t)words[1];
+    if (n_bytes > 0x7FFFFFF0ull) return fail(h, PISCES_E_INVALID_ARG, "bam_decode: more than 2^31 bytes of distinct amplicon names (XN tags) in one call");
+    std::vector<int32_t> slot_id(slots, -1);
+    if (n_names > 0) {
+        PISCES_HIP_CHECK(h, B.amp_names.reserve(n_names));
+        PISCES_HIP_CHECK(h, B.amp_name_bytes.reserve(n_bytes + 1));
+        PISCES_HIP_CHECK(h, hipMemsetAsync(B.amp_counters.p, 0, 2 * sizeof(uint32_t), h->stream));
+        hipLaunchKernelGGL(amplicon_compact_kernel, dim3((unsigned)((slots + 255) / 256)), dim3(256), 0, h->stream, (const uint8_t*)B.d_stream.p,
+                           (const unsigned long long*)B.amp_table.p, (const int32_t*)B.amp_slot_first.p, (uint32_t)slots, B.amp_names.p, (uint32_t)n_names,
+                           B.amp_name_bytes.p, (uint32_t)n_bytes, B.amp_counters.p);
+        PISCES_HIP_CHECK(h, hipGetLastError());
+        std::vector<AmpliconName> names(n_names);
+        std::vector<uint8_t> bytes(n_bytes + 1);
+        PISCES_HIP_CHECK(h, hipMemcpyAsync(names.data(), B.amp_names.p, n_names * sizeof(AmpliconName), hipMemcpyDeviceToHost, h->stream));
+        if (n_bytes) PISCES_HIP_CHECK(h, hipMemcpyAsync(bytes.data(), B.amp_name_bytes.p, n_bytes, hipMemcpyDeviceToHost, h->stream));
+        PISCES_HIP_CHECK(h, hipStreamSynchronize(h->stream));
+        h->pcie[1] += (int64_t)(n_names * sizeof(AmpliconName) + n_bytes);
+        std::sort(names.begin(), names.end(), [](const AmpliconName& a, const AmpliconName& b) { return a.first_read < b.first_read; });
+        for (const AmpliconName& nm : names) {
+            if (nm.slot < 0 || (size_t)nm.slot >= slots || nm.length < 0 || nm.byte_offset < 0 || (size_t)nm.byte_offset + (size_t)nm.length > n_bytes)
+                return fail(h, PISCES_E_DEVICE, "bam_decode: the amplicon name table is inconsistent");
+            slot_id[(size_t)nm.slot] = amplicon_name_id(h, std::string((const char*)bytes.data() + nm.byte_offset, (size_t)nm.length));
+        }
+    }
+    PISCES_HIP_CHECK(h, B.amp_slot_id.reserve(slots));
+    PISCES_HIP_CHECK(h, hipMemcpyAsync(B.amp_slot_id.p, slot_id.data(), slots * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+    h->pcie[0] += (int64_t)(slots * sizeof(int32_t));
+    hipLaunchKernelGGL(amplicon_assign_ids_kernel, dim3(grid), dim3(256), 0, h->stream, (const int32_t*)B.amp_slot.p, (const int32_t*)B.amp_slot_id.p, nr, B.amp_ids.p);
+    PISCES_HIP_CHECK(h, hipGetLastError());
+    PISCES_HIP_CHECK(h, hipStreamSynchronize(h->stream));   // (slot_id is a local)
+    B.has_amp = true;
+    return PISCES_OK;
+}
+
 // ---- BAM bytes -> read batch on the device (row f4): only the compressed file crosses PCIe -------------------------------
 int32_t pisces_hip_bam_decode(PiscesHip* h, const uint8_t* file, int64_t n_bytes, const PiscesBgzfBlock* blocks, int64_t n_blocks, int32_t ref_id,
                               int32_t min_map_quality, int32_t skip_duplicates, int32_t only_proper_pairs, int64_t counts[4])
@@ -143,6 +222,7 @@ int32_t pisces_hip_bam_decode(PiscesHip* h, const uint8_t* file, int64_t n_bytes
     h->bam.valid = false;
     h->bam.moved = false;
     h->bam.added = false;
+    h->bam.has_amp = false;
     int64_t out_bytes = 0;
     for (int64_t i = 0; i < n_blocks; i++) {
         const PiscesBgzfBlock& b = blocks[i];
@@ -266,13 +346,15 @@ int32_t pisces_hip_bam_decode(PiscesHip* h, const uint8_t* file, int64_t n_bytes
     PISCES_HIP_CHECK(h, B.d_block_map.reserve(map_words));
     PISCES_HIP_CHECK(h, hipMemsetAsync(B.d_block_map.p, 0, map_words * sizeof(uint32_t), h->stream));
     PISCES_HIP_CHECK(h, hipMemsetAsync(B.d_first_error.p, 0xFF, sizeof(unsigned long long), h->stream));
+    const bool track = h->amp_on;   // the XN tag of every kept read (a handle that tracks nothing passes nullptr and launches nothing more)
+    if (track) PISCES_HIP_CHECK(h, B.amp_tag.reserve(nr + 1));
     if (nr > 0)
         hipLaunchKernelGGL(bam_decode_kernel, dim3((unsigned)n_chunks), dim3(256), 0, h->stream, (const uint8_t*)B.d_stream.p, out_bytes,
                            (const long long*)B.d_entry.p, F, (const int32_t*)B.d_n_reads.p, (const int32_t*)B.d_n_ops.p, (const int32_t*)B.d_n_bases.p,
                            B.position.p, B.flags.p, B.cigar_offset.p, B.cigar_op.p, B.cigar_len.p, B.seq_offset.p, B.bases.p + kSegmentPad, B.quals.p + kSegmentPad,
                            B.op_quality.p, B.read_quality.p, (const long long*)B.d_n_span.p, (const int32_t*)B.d_n_indels.p, B.d_slots.p,
                            B.d_fslots.p, B.d_block_map.p, n_block_bits, B.d_first_error.p, B.has_dirs ? B.dirs.p + kSegmentPad : (uint8_t*)nullptr,
-                           B.has_dirs ? B.del_dirs.p : (uint8_t*)nullptr);
+                           B.has_dirs ? B.del_dirs.p : (uint8_t*)nullptr, track ? B.amp_tag.p : (unsigned long long*)nullptr);
     // the closing offsets
     const int32_t end_ops = (int32_t)no, end_bases = (int32_t)nb, end_fslots = (int32_t)B.found_slots;
     const long long end_slots = B.log_slots;
@@ -286,6 +368,7 @@ int32_t pisces_hip_bam_decode(PiscesHip* h, const uint8_t* file, int64_t n_bytes
     PISCES_HIP_CHECK(h, hipMemcpyAsync(&B.first_error, B.d_first_error.p, sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
     PISCES_HIP_CHECK(h, hipGetLastError());
     PISCES_HIP_CHECK(h, hipStreamSynchronize(h->stream));
+    if (track) { int32_t rca = bam_intern_amplicons(h); if (rca) return rca; }
     B.valid = true;
     if (counts) { counts[0] = B.n_reads; counts[1] = B.n_skipped; counts[2] = B.n_ops; counts[3] = B.n_bases; }
     return PISCES_OK;
@@ -347,11 +430,57 @@ int32_t pisces_hip_bam_fetch_directions(PiscesHip* h, uint8_t* directions, uint8
     });
 }
 
+int32_t pisces_hip_bam_fetch_amplicons(PiscesHip* h, int32_t* amplicon_id)
+{
+    return abi_guard<int32_t>(h, [&]() -> int32_t {
+    if (!h) return PISCES_E_INVALID_ARG;
+    if (!h->bam.valid) return fail(h, PISCES_E_STATE, "bam_fetch_amplicons: no decoded batch (pisces_hip_bam_decode first)");
+    auto& B = h->bam;
+    if (B.moved) return fail(h, PISCES_E_STATE, "bam_fetch_amplicons: the decoded batch has been added to the read store");
+    if (!B.has_amp) return 0;
+    PISCES_HIP_CHECK(h, hipSetDevice(h->device));
+    if (amplicon_id && B.n_reads) PISCES_HIP_CHECK(h, hipMemcpyAsync(amplicon_id, B.amp_ids.p, (size_t)B.n_reads * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    PISCES_HIP_CHECK(h, hipStreamSynchronize(h->stream));
+    return 1;
+    });
+}
+
+int32_t pisces_hip_amplicon_name_count(PiscesHip* h)
+{
+    return abi_guard<int32_t>(h, [&]() -> int32_t {
+    if (!h) return PISCES_E_INVALID_ARG;
+    return (int32_t)h->amp_names.size();
+    });
+}
+
+int32_t pisces_hip_get_amplicon_name(PiscesHip* h, int32_t id, char* out, int32_t capacity)
+{
+    return abi_guard<int32_t>(h, [&]() -> int32_t {
+    if (!h) return PISCES_E_INVALID_ARG;
+    if (id < 0 || (size_t)id >= h->amp_names.size()) return fail(h, PISCES_E_INVALID_ARG, "get_amplicon_name: no amplicon name has id " + std::to_string(id));
+    const std::string& name = h->amp_names[(size_t)id];
+    if (out && capacity >= (int32_t)name.size() && !name.empty()) std::memcpy(out, name.data(), name.size());
+    return (int32_t)name.size();
+    });
+}
+
+int32_t pisces_hip_intern_amplicon_name(PiscesHip* h, const char* name, int32_t length)
+{
+    return abi_guard<int32_t>(h, [&]() -> int32_t {
+    if (!h) return PISCES_E_INVALID_ARG;
+    if (length < 0 || (length > 0 && !name)) return fail(h, PISCES_E_INVALID_ARG, "intern_amplicon_name: bad arguments");
+    if (!h->amp_on) return fail(h, PISCES_E_STATE, "intern_amplicon_name: the handle tracks no amplicon counts (pisces_hip_set_amplicon_bias_filter)");
+    return amplicon_name_id(h, length ? std::string(name, (size_t)length) : std::string());
+    });
+}
+
 int32_t pisces_hip_add_decoded_reads(PiscesHip* h)
 {
     return abi_guard<int32_t>(h, [&]() -> int32_t {
     if (!h) return PISCES_E_INVALID_ARG;
-    if (h->amp_on) return fail(h, PISCES_E_UNSUPPORTED, "add_decoded_reads: the handle tracks amplicon counts (pisces_hip_set_amplicon_bias_filter): the XN tag is not decoded on the device yet");
+    if (h->amp_on && !(h->bam.valid && h->bam.has_amp))
+        return fail(h, PISCES_E_UNSUPPORTED, "add_decoded_reads: the handle tracks amplicon counts (pisces_hip_set_amplicon_bias_filter) and there is no decoded batch with amplicon ids: "
+                                             "the XN tags are read by a pisces_hip_bam_decode that runs after tracking was switched on");
     if (!h->bam.valid) return fail(h, PISCES_E_STATE, "add_decoded_reads: no decoded batch (pisces_hip_bam_decode first)");
     HostTimer timer(&h->host_time[0]);
     auto& B = h->bam;
@@ -369,6 +498,7 @@ int32_t pisces_hip_add_decoded_reads(PiscesHip* h)
             case kBamReadCigarLongerThanRead: return fail(h, PISCES_E_INVALID_ARG, "add_decoded_reads: CIGAR does not match the read" + read);
             case kBamReadPastInt32: return fail(h, PISCES_E_INVALID_ARG, "add_decoded_reads: read runs past position 2^31 - 1" + read);
             case kBamReadBadDirectionTag: return fail(h, PISCES_E_INVALID_ARG, "add_decoded_reads: unexpected format in a direction string (XD tag)" + read);
+            case kBamReadBadAmpliconTag: return fail(h, PISCES_E_INVALID_ARG, "add_decoded_reads: the XN tag (amplicon name) is neither a string nor a character" + read);
             default: return fail(h, PISCES_E_INVALID_ARG, "add_decoded_reads: read runs far past the end of its reference sequence" + read);
         }
     }
@@ -387,7 +517,9 @@ int32_t pisces_hip_add_decoded_reads(PiscesHip* h)
         B.added = true;   // consumed: a second add of the same decoded batch is refused, whichever way it went into the store
     };
     if (h->read_path == 1) {
+        h->amp_pending = h->amp_on ? B.amp_ids.p : nullptr;   // (amplicon_store_ids: the ids of this batch, on the device already)
         const int32_t rcs = add_decoded_reads_store(h, found_slots, found_pool, find_on_device);
+        h->amp_pending = nullptr;
         if (rcs == PISCES_OK) commit();
         return rcs;
     }

@@ -976,6 +976,7 @@ static int32_t add_decoded_reads_store(PiscesHip* h, int64_t found_slots, int64_
         db.seq_offset = A.seq_offset; db.bases = A.bases; db.quals = A.quals; db.dirs = A.dirs; db.n_reads = nr;
         rc = enqueue_candidate_discovery(h, db, B.has_dirs ? B.del_dirs.p : nullptr, nr, (const int32_t*)B.d_fslots.p, found_slots, found_pool);
     }
+    if (rc == PISCES_OK && h->amp_on) rc = amplicon_store_ids(h, g, A.cigar_offset, nr, n_cig);
     if (rc) {
         (void)hipStreamSynchronize(h->stream);
         if (pl.direct) { g.bases.swap(B.bases); g.quals.swap(B.quals); g.cop.swap(B.cigar_op); g.clen.swap(B.cigar_len); if (B.has_dirs) g.dirs.swap(B.dirs); B.moved = false; }

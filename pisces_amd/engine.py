@@ -644,6 +644,39 @@ class HipVariantCaller:
             _check(self._h, rc)
         return (dirs, dd) if rc == 1 else None
 
+    def bam_fetch_amplicons(self):
+        """The amplicon id of every read of the decoded batch (its XN tag as an id of AmpliconNames(), -1 without the tag), or None when
+        the batch has none: the handle did not track amplicon counts when it was decoded."""
+        ids = np.zeros(self._bam_counts["reads"], np.int32)
+        rc = lib.pisces_hip_bam_fetch_amplicons(self._h, ids.ctypes.data)
+        if rc < 0:
+            _check(self._h, rc)
+        return ids if rc == 1 else None
+
+    def AmpliconNames(self):
+        """The handle's amplicon names (bytes), index = id: what the decodes met, in order of first appearance, and InternAmpliconName's."""
+        n = lib.pisces_hip_amplicon_name_count(self._h)
+        if n < 0:
+            _check(self._h, n)
+        names = []
+        for i in range(n):
+            length = lib.pisces_hip_get_amplicon_name(self._h, i, None, 0)
+            if length < 0:
+                _check(self._h, length)
+            buf = C.create_string_buffer(max(length, 1))
+            _check(self._h, min(lib.pisces_hip_get_amplicon_name(self._h, i, buf, length), 0))
+            names.append(buf.raw[:length])
+        return names
+
+    def InternAmpliconName(self, name):
+        """The id of `name` (bytes or str) in the handle's dictionary, a new one when the name is new: for reads the host parses itself and
+        hands to AddAlleleCounts(reads, amplicon_ids=...) beside decoded batches."""
+        raw = name.encode() if isinstance(name, str) else bytes(name)
+        rc = lib.pisces_hip_intern_amplicon_name(self._h, raw, len(raw))
+        if rc < 0:
+            _check(self._h, rc)
+        return rc
+
     def bam_fetch(self):
         """The decoded batch as host arrays (dict with the PiscesReadBatch field names)."""
         n = self._bam_counts
