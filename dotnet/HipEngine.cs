@@ -39,6 +39,7 @@ namespace Pisces.Hip
         private bool _trackAmplicons;
         private readonly Dictionary<string, int> _ampliconIds = new Dictionary<string, int>();
         private readonly List<string> _ampliconNames = new List<string>();
+        private bool _exactCoverage;
         private readonly List<int> _ampId = new List<int>();
         // BlocksPerFlush > 1 holds the native flush back until upTo has moved that many blocks on: records come out later, in the same
         // order (the VCF writer does not care), and the per-flush latency (~0.26 ms) is paid once per group (DESIGN.md section 8)
@@ -95,6 +96,24 @@ namespace Pisces.Hip
         {
             _trackAmplicons = threshold.HasValue;
             NativeMethods.Check(_h, NativeMethods.pisces_hip_set_amplicon_bias_filter(_h, threshold ?? -1f));
+        }
+
+        /// PiscesApplicationOptions.CoverageMethod: before the first read.  An exact handle counts the reads that span every insertion, deletion
+        /// and MNV of a flush on the device (ExactCoverageCalculator); what it cannot go together with comes back as PISCES_E_UNSUPPORTED.
+        public void SetCoverageMethod(bool exact)
+        {
+            _exactCoverage = exact;
+            NativeMethods.Check(_h, NativeMethods.pisces_hip_set_coverage_method(_h, exact ? NativeMethods.PISCES_COVERAGE_EXACT : NativeMethods.PISCES_COVERAGE_APPROXIMATE));
+        }
+
+        /// What ExactCoverageCalculator needs of IAlleleSource.GetSpanningReadSummaries(preceding, trailing): the spanning reads by direction
+        public int[] GetSpanningReadCounts(int preceding, int trailing, bool isInsertion = false)
+        {
+            if (!_exactCoverage) throw new ArgumentException("Not configured to track read summaries.");   // RegionStateManager.cs:236-237
+            FlushStagedReads(null);
+            var counts = new int[3];
+            NativeMethods.Check(_h, NativeMethods.pisces_hip_get_spanning_read_counts(_h, preceding, trailing, isInsertion ? 1 : 0, counts));
+            return counts;
         }
 
         /// IAlleleSource.GetCoverageByAmplicon: the native slots (ascending id) back to names

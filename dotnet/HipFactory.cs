@@ -66,6 +66,7 @@ namespace Pisces.Hip
             _engine.SetAdaptiveGenotypingParameters(_options.VariantCallingParameters.AdaptiveGenotypingParameters);   // (DiploidByAdaptiveGT only)
             _engine.SetForcedAlleles(_forcedGtAlleles);   // -forcedalleles: ForcedReport rows, reference rows at forced positions
             _engine.SetAmpliconBiasFilter(_options.VariantCallingParameters.AmpliconBiasFilterThreshold);   // Factory.ShouldTrackAmpliconCounts (null: off)
+            _engine.SetCoverageMethod(_options.CoverageMethod == Pisces.Domain.Types.CoverageMethod.Exact);   // Factory.CreateCoverageCalculator / trackReadSummaries (Factory.cs:130,184-185)
             return new HipStateManager(_engine);
         }
 
@@ -162,7 +163,9 @@ namespace Pisces.Hip
         // (CollapedRegionStateManager.cs:33); RegionStateManager itself returns 0 (RegionStateManager.cs: the virtual no-op
         // AddCollapsedReadCount), and so does this state manager: Factory.CreateStateManager is asked for the plain one here.
         public int GetCollapsedReadCount(int position, Pisces.Domain.Types.ReadCollapsedType type) { return 0; }
-        // Consumer: ExactCoverageCalculator (only with the exact-coverage option, which HipAlleleCaller does not run): not carried.
+        // Consumer: ExactCoverageCalculator, which the native flush of an exact handle replaces (pisces_hip_set_coverage_method): the summaries
+        // themselves are not carried — their only consumer is a count by direction, HipEngine.GetSpanningReadCounts
+        // (pisces_hip_get_spanning_read_counts).
         public List<ReadCoverageSummary> GetSpanningReadSummaries(int startPosition, int endPosition) { return new List<ReadCoverageSummary>(); }
         // The amplicon-bias calculator's coverage (-abfilter): the native per-amplicon counts of the read store, the XN names restored from
         // the engine's per-chromosome dictionary; empty when the filter is off, as RegionStateManager's is without tracking.  The filter

@@ -854,6 +854,45 @@ int32_t pisces_hip_amplicon_name_count(PiscesHip* h);
 int32_t pisces_hip_get_amplicon_name(PiscesHip* h, int32_t id, char* out, int32_t capacity);
 int32_t pisces_hip_intern_amplicon_name(PiscesHip* h, const char* name, int32_t length);
 
+/* ---- CoverageMethod.Exact (PiscesApplicationOptions.CoverageMethod, -coveragemethod exact) on the streaming surface ----
+ * pisces_hip_exact_span_direction: ExactCoverageCalculator's decision for ONE read's coverage summary and ONE span, host only, no handle
+ * (ExactCoverageCalculator.cs:62-96 with GetIndexBoundaries and GetDirection).  cs / ce: the summary's clip-adjusted start and end; the
+ * CIGAR as operation characters and lengths; the directions as runs (DirectionInfo: dir_run_type[i] a PISCES_DIR_* value).  preceding /
+ * trailing: the allele's span (deletion at p of length L: p, p + L + 1; MNV: p - 1, p + L; insertion: p, p + 1); is_insertion is taken
+ * and, as in the reference, never read.  Returns the direction the read counts in (0 / 1 / 2), -1 when it does not span the allele, -2
+ * where the reference throws InvalidDataException (a read of several direction runs with no base at or before `preceding` and none at
+ * or behind `trailing`), -3 for arguments the reference would index out of bounds with (several runs longer than the CIGAR's read
+ * span, a direction above 2, null arrays); runs that fall short leave the rest of the read Forward, as a new direction map does.  The summary is taken as given: it need not be one a read can leave behind.
+ * csrc/exact_span.h, written for host and device: exact_span_kernel compiles the same source. */
+int32_t pisces_hip_exact_span_direction(int32_t cs, int32_t ce, const uint8_t* cigar_op, const uint32_t* cigar_len, int32_t n_cigar,
+                                        const uint8_t* dir_run_type, const uint32_t* dir_run_len, int32_t n_runs, int32_t preceding,
+                                        int32_t trailing, int32_t is_insertion);
+/* pisces_hip_set_coverage_method: PISCES_COVERAGE_EXACT makes the handle an EXACT one.  Every read that joins the read store then leaves
+ * a summary next to its descriptor (clip-adjusted ends, first / last operation an insertion, one direction or several), touches the block
+ * of its clip-adjusted END as well (RegionStateManager.AddAlleleCounts stores the summary through GetBlock, :212-219: a trailing soft clip
+ * that reaches into the next block makes that block exist, and it is flushed like any other), and the coverage of every insertion,
+ * deletion and MNV row of a flush is the number of reads that span the allele, by direction, counted on the device (exact_span_kernel):
+ * EstimatedCoverageByDirection holds the three counts as they are (no stitched redistribution: coverage_by_dir[2] is filled),
+ * TotalCoverage their sum, ReferenceSupport max(0, TotalCoverage - AlleleSupport); q-score, strand bias, genotype, filters and the
+ * collapser's frequencies follow.  SNV and Reference rows are what an Approximate handle gives.  A read is seen by a span while the
+ * block of its clip-adjusted end is held and that end lies at or below trailing + 2 * (length of the first read the handle was given)
+ * (GetSpanningReadSummaries, :234-254).  A flush that meets the reference's InvalidDataException (-2 above) returns PISCES_E_INVALID_ARG
+ * naming the allele's position; the blocks stay held.  Before the first read is added (PISCES_E_STATE afterwards); an unknown value:
+ * PISCES_E_INVALID_ARG.  PISCES_E_UNSUPPORTED, each with a message, for what Exact cannot go together with — here when the handle has it
+ * already, at the other entry when it comes later: NoiseModel.Window (the Exact calculator's own base-quality sum is not carried),
+ * forced alleles, pisces_hip_set_owned_range (a shard's halo is cut by aligned span, not by clip-adjusted span), PISCES_HIP_READ_PATH=log
+ * and pisces_hip_add_observations (observation tuples have no reads), and the tile surface pisces_hip_call_tiles* (tuples have no reads).
+ * An exact handle waits for the device where an Approximate one does not: every add of reads ends with one small transfer and a wait (the
+ * word that says whether a read's clip-adjusted end made a block), so adds do not return ahead of their kernels; and a flush whose batch
+ * holds an insertion, deletion or MNV candidate (never one pisces_hip_flush_begin leaves to the device alone) waits once more per
+ * candidate pass — once ahead of the collapse, once ahead of each call_spanning_kernel pass — for the counts and their error word.
+ * pisces_hip_get_spanning_read_counts waits for its launch.  What it costs on one mix: DESIGN section 7.
+ * pisces_hip_get_spanning_read_counts: what a host needs of IAlleleSource.GetSpanningReadSummaries — out[3] = the reads that span
+ * [preceding, trailing] by direction, from the reads the store holds now.  PISCES_E_STATE on a handle that is not exact. */
+enum { PISCES_COVERAGE_APPROXIMATE = 0, PISCES_COVERAGE_EXACT = 1 };
+int32_t pisces_hip_set_coverage_method(PiscesHip* h, int32_t method);
+int32_t pisces_hip_get_spanning_read_counts(PiscesHip* h, int32_t preceding, int32_t trailing, int32_t is_insertion, int32_t* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -24,6 +24,7 @@ ALLELE_OF_BASE = {"A": ALLELE_A, "G": ALLELE_G, "C": ALLELE_C, "T": ALLELE_T, "N
 BASE_OF_ALLELE = "AGCTND"
 # src/lib/Pisces.Domain/Types/DirectionType.cs:3-8
 DIR_FORWARD, DIR_REVERSE, DIR_STITCHED = range(3)
+COVERAGE_APPROXIMATE, COVERAGE_EXACT = range(2)   # pisces_hip_set_coverage_method (PiscesApplicationOptions.CoverageMethod)
 # src/lib/Pisces.Domain/Types/CallType.cs:3-12
 CAT_SNV, CAT_INSERTION, CAT_DELETION, CAT_MNV, CAT_REFERENCE = range(5)
 # src/lib/Pisces.Domain/Types/Genotype.cs:3-18

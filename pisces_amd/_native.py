@@ -28,6 +28,7 @@ EXPORTS = [
     "pisces_hip_amplicon_bias", "pisces_hip_set_amplicon_bias_filter", "pisces_hip_add_reads_amplicons", "pisces_hip_add_device_reads_amplicons",
     "pisces_hip_get_amplicon_counts", "pisces_hip_bam_fetch_amplicons", "pisces_hip_amplicon_name_count", "pisces_hip_get_amplicon_name",
     "pisces_hip_intern_amplicon_name",
+    "pisces_hip_exact_span_direction", "pisces_hip_set_coverage_method", "pisces_hip_get_spanning_read_counts",
 ]
 
 
@@ -128,6 +129,9 @@ def _load():
         "pisces_hip_amplicon_name_count": (i32, [vp]),
         "pisces_hip_get_amplicon_name": (i32, [vp, i32, vp, i32]),
         "pisces_hip_intern_amplicon_name": (i32, [vp, C.c_char_p, i32]),
+        "pisces_hip_exact_span_direction": (i32, [i32, i32, vp, vp, i32, vp, vp, i32, i32, i32, i32]),
+        "pisces_hip_set_coverage_method": (i32, [vp, i32]),
+        "pisces_hip_get_spanning_read_counts": (i32, [vp, i32, i32, i32, P(i32)]),
         "pisces_hip_call_tiles_graph_build": (i32, [vp, P(_abi.PiscesTileBatch), i32, P(i32)]),
         "pisces_hip_call_tiles_graph_launch": (i32, [vp, i32, vp]),
         "pisces_hip_mark": (i32, [vp, i32, vp]),

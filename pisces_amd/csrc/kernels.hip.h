@@ -1634,7 +1634,8 @@ __global__ __launch_bounds__(64) void call_spanning_kernel(
     const uint8_t* __restrict__ ref, int64_t ref_len /* ref[i] = position i+1 */, int32_t expect_stitched,
     PiscesCalledAllele* __restrict__ out, uint8_t* __restrict__ callable_out, DeviceParams P,
     const double* __restrict__ sumq = nullptr /* NoiseModel.Window */, const int32_t* __restrict__ counts_folded = nullptr,
-    int32_t wanted = kSpanningEveryRecord)
+    int32_t wanted = kSpanningEveryRecord,
+    const int32_t* __restrict__ exact_cov = nullptr /* CoverageMethod.Exact: [n][4], the reads that span candidate i by direction (exact_span_kernel); nullptr: Approximate */)
 {
     const int i = blockIdx.x * 64 + threadIdx.x;
     if (i >= n) return;
@@ -1707,7 +1708,14 @@ __global__ __launch_bounds__(64) void call_spanning_kernel(
     const int length = c.category == PISCES_CAT_INSERTION ? c.alt_len - 1 : c.category == PISCES_CAT_DELETION ? c.ref_len - 1 : c.alt_len;
     const int support = c.sup[0] + c.sup[1] + c.sup[2];
     double sumQ = 0.0;
-    const SpanningCoverage sc = spanning_coverage(c, counts, expect_stitched, sumq, &sumQ);
+    // CoverageMethod.Exact (ExactCoverageCalculator.cs:44-102): the three counts as they are, no RedistributeStitchedCoverage, their sum
+    SpanningCoverage sc;
+    if (exact_cov) {
+        for (int d = 0; d < 3; d++) sc.cov[d] = exact_cov[4 * i + d];
+        sc.total = sc.cov[0] + sc.cov[1] + sc.cov[2];
+    } else {
+        sc = spanning_coverage(c, counts, expect_stitched, sumq, &sumQ);
+    }
     const int cov[3] = {sc.cov[0], sc.cov[1], sc.cov[2]};
     const int total = sc.total;
     int refsup = total - support;
@@ -1776,7 +1784,7 @@ __global__ __launch_bounds__(64) void call_spanning_kernel(
     r.allele_support = support;
     r.reference_support = refsup;
     r.num_no_calls = 0;
-    r.coverage_by_dir[0] = cov[0]; r.coverage_by_dir[1] = cov[1]; r.coverage_by_dir[2] = 0;
+    r.coverage_by_dir[0] = cov[0]; r.coverage_by_dir[1] = cov[1]; r.coverage_by_dir[2] = exact_cov ? cov[2] : 0;
     r.support_by_dir[0] = c.sup[0]; r.support_by_dir[1] = c.sup[1]; r.support_by_dir[2] = c.sup[2];
     r.variant_qscore = vq;
     r.strand_bias_score = sb.bias_score;

@@ -36,6 +36,7 @@
 #include "stream_kernels.hip.h"
 #include "store_kernels.hip.h"
 #include "amplicon_kernels.hip.h"
+#include "exact_kernels.hip.h"
 #include "finder_kernels.hip.h"
 #include "bgzf_kernels.hip.h"
 #include "bam_kernels.hip.h"
@@ -262,6 +263,8 @@ struct ReadSegment {
     DeviceBuf<ReadExt> ext;
     DeviceBuf<ReadDesc> frag;    // one per CIGAR operation: what the flush kernel walks
     DeviceBuf<int32_t> amp_read_ids, amp_frag_ids;   // a tracking handle (pisces_hip_set_amplicon_bias_filter): the amplicon id of every read / fragment
+    DeviceBuf<ExactSummary> x_sum;   // an exact handle (pisces_hip_set_coverage_method): the coverage summary of every read (exact_kernels.hip.h) ...
+    DeviceBuf<int32_t> x_bounds;     // ... and the longest CE - Position / leading clip of the segment's reads: what widens a span's read range
     DeviceBuf<int32_t> grid;     // the position grid (store_kernels.hip.h grid_cells): first fragment per position (cell) from cell grid_base on
     int64_t grid_base = 0, grid_n = 0;
     bool grid_ok = false;        // every batch so far could extend it (known first position, not before grid_base, a sane span)
@@ -316,6 +319,12 @@ struct PiscesHip {
     // pisces_hip_intern_amplicon_name; a name keeps its id for the handle's life
     std::vector<std::string> amp_names;
     std::unordered_map<std::string, int32_t> amp_name_id;
+    // pisces_hip_set_coverage_method(PISCES_COVERAGE_EXACT): every read leaves a coverage summary in its segment and the coverage of the spanning
+    // rows of a flush is counted from them (exact_span_kernel)
+    bool exact_on = false;
+    bool exact_l0_set = false;                 // d_exact_words[0] holds the length of the first read the handle saw (RegionStateManager._readLength)
+    DeviceBuf<int32_t> d_exact_words;          // [0] that length, [1] the last add's "some read's clip-adjusted end makes a block", [2] a launch's error word
+    DeviceBuf<int32_t> d_exact_extra, d_exact_spans, d_exact_out;
     DeviceBuf<PiscesTile> d_tiles_x;
     DeviceBuf<PiscesTileResult> d_tr_x;
     DeviceBuf<PiscesCalledAllele> d_rec_x;
@@ -1186,6 +1195,8 @@ int32_t pisces_hip_set_owned_range(PiscesHip* h, int32_t lo, int32_t hi)
 {
     return abi_guard<int32_t>(h, [&]() -> int32_t {
     if (!h || lo < 1 || hi < lo) return fail(h, PISCES_E_INVALID_ARG, "set_owned_range: bad range");
+    if (h->exact_on) return fail(h, PISCES_E_UNSUPPORTED, "set_owned_range: the handle counts spanning reads (pisces_hip_set_coverage_method, Exact): a shard's halo is cut by aligned span, "
+                                                          "not by the clip-adjusted span a spanning read is found by");
     h->own_lo = lo;
     h->own_hi = hi;
     return PISCES_OK;
@@ -1205,6 +1216,8 @@ int32_t pisces_hip_set_owned_range(PiscesHip* h, int32_t lo, int32_t hi)
 #include "surface_comm.inc.h"
 
 #include "surface_amplicon.inc.h"
+
+#include "surface_exact.inc.h"
 
 int32_t pisces_hip_synchronize(PiscesHip* h)
 {

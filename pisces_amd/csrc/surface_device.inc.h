@@ -12,6 +12,7 @@ int32_t pisces_hip_call_tiles(PiscesHip* h, const uint32_t* d_tuples, const Pisc
     return abi_guard<int32_t>(h, [&]() -> int32_t {
     if (!h) return PISCES_E_INVALID_ARG;
     if (n_tiles < 0 || record_capacity < 0 || ref_length < 0) return fail(h, PISCES_E_INVALID_ARG, "call_tiles: negative size");
+    if (h->exact_on) return fail(h, PISCES_E_UNSUPPORTED, "call_tiles" ": the handle counts spanning reads (pisces_hip_set_coverage_method, Exact): the tile surface takes observation tuples, which have no reads");
     if (n_tiles > 0 && (!d_tiles || !d_ref_bases || !d_records || !d_tile_results))
         return fail(h, PISCES_E_INVALID_ARG, "call_tiles: null device pointer");
     if ((int64_t)record_capacity < (int64_t)n_tiles * kSlotsPerTile)
@@ -65,6 +66,7 @@ int32_t pisces_hip_call_tiles_batched(PiscesHip* h, const PiscesTileBatch* batch
     return abi_guard<int32_t>(h, [&]() -> int32_t {
     if (!h) return PISCES_E_INVALID_ARG;
     if (n_batches < 0 || (n_batches > 0 && !batches)) return fail(h, PISCES_E_INVALID_ARG, "call_tiles_batched: null batch list");
+    if (h->exact_on) return fail(h, PISCES_E_UNSUPPORTED, "call_tiles_batched" ": the handle counts spanning reads (pisces_hip_set_coverage_method, Exact): the tile surface takes observation tuples, which have no reads");
     if (h->cfg.ploidy == PISCES_PLOIDY_DIPLOID_ADAPTIVE)
         return fail(h, PISCES_E_UNSUPPORTED, "call_tiles_batched: PloidyModel.DiploidByAdaptiveGT has one posteriors buffer a handle; use pisces_hip_call_tiles");
     if (h->cfg.noise_model == PISCES_NOISE_WINDOW)
@@ -106,6 +108,7 @@ int32_t pisces_hip_call_tiles_graph_build(PiscesHip* h, const PiscesTileBatch* b
     return abi_guard<int32_t>(h, [&]() -> int32_t {
     if (!h || !graph_id) return PISCES_E_INVALID_ARG;
     if (n_batches <= 0 || !batches) return fail(h, PISCES_E_INVALID_ARG, "call_tiles_graph_build: null batch list");
+    if (h->exact_on) return fail(h, PISCES_E_UNSUPPORTED, "call_tiles_graph_build" ": the handle counts spanning reads (pisces_hip_set_coverage_method, Exact): the tile surface takes observation tuples, which have no reads");
     if (h->cfg.ploidy == PISCES_PLOIDY_DIPLOID_ADAPTIVE)
         return fail(h, PISCES_E_UNSUPPORTED, "call_tiles_graph_build: PloidyModel.DiploidByAdaptiveGT has one posteriors buffer a handle; use pisces_hip_call_tiles");
     if (h->cfg.noise_model == PISCES_NOISE_WINDOW)
@@ -163,6 +166,7 @@ int32_t pisces_hip_call_tiles_graph_launch(PiscesHip* h, int32_t graph_id, void*
     return abi_guard<int32_t>(h, [&]() -> int32_t {
     if (!h) return PISCES_E_INVALID_ARG;
     if (graph_id < 0 || (size_t)graph_id >= h->graphs.size()) return fail(h, PISCES_E_INVALID_ARG, "call_tiles_graph_launch: no such graph");
+    if (h->exact_on) return fail(h, PISCES_E_UNSUPPORTED, "call_tiles_graph_launch" ": the handle counts spanning reads (pisces_hip_set_coverage_method, Exact): the tile surface takes observation tuples, which have no reads");
     PISCES_HIP_CHECK(h, hipSetDevice(h->device));
     if (stream && (hipStream_t)stream != h->stream) h->foreign_stream_used = h->foreign_stream_ever = true;
     PISCES_HIP_CHECK(h, hipGraphLaunch(h->graphs[(size_t)graph_id], stream ? (hipStream_t)stream : h->stream));

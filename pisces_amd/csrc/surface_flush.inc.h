@@ -1130,6 +1130,7 @@ struct SpanBatch {
     std::map<int32_t, CandPtr> touched_refs; // Reference candidates created for the reallocator, by position
     std::vector<CandPtr> failed;
     std::vector<const HostCandidate*> final_list;
+    int32_t exact_rc = PISCES_OK;            // an exact handle: what the collapser's coverage look-ups ran into (span_collapse cannot return it)
 };
 
 static int span_atype(char ch) { return ch == 'A' ? 0 : ch == 'G' ? 1 : ch == 'C' ? 2 : ch == 'T' ? 3 : 4; }
@@ -1223,6 +1224,33 @@ static void to_dev(SpanBatch& B, const HostCandidate& c, DevCandidate& d)
         auto it = B.h->gapped_mnv_ref.find(c.position);
         d.gapped = it == B.h->gapped_mnv_ref.end() ? 0 : it->second;
     }
+}
+
+// CoverageMethod.Exact: the span an allele asks the reads with (ExactCoverageCalculator.Compute :18-42); {1, 0} — no span — for point alleles
+static void exact_span_of(const HostCandidate& c, int32_t* span)
+{
+    const int64_t p = c.position;
+    int64_t a = 1, b = 0;
+    if (c.category == PISCES_CAT_DELETION) { a = p; b = p + ((int64_t)c.ref.size() - 1) + 1; }
+    else if (c.category == PISCES_CAT_MNV) { a = p - 1; b = p + (int64_t)c.alt.size(); }
+    else if (c.category == PISCES_CAT_INSERTION) { a = p; b = p + 1; }
+    span[0] = (int32_t)std::min<int64_t>(a, 0x7FFFFFFFll);
+    span[1] = (int32_t)std::min<int64_t>(b, 0x7FFFFFFFll);
+}
+// exact_span_kernel over a list of candidates: cov[4 i ..] = the reads that span candidate i by direction (left in h->d_exact_out too, where
+// call_spanning_kernel reads them).  A read that runs into the reference's InvalidDataException fails the flush, naming the allele.
+static int32_t exact_candidate_coverage(PiscesHip* h, const std::vector<const HostCandidate*>& list, std::vector<int32_t>& cov)
+{
+    std::vector<int32_t> spans(2 * list.size());
+    for (size_t i = 0; i < list.size(); i++) exact_span_of(*list[i], &spans[2 * i]);
+    cov.assign(4 * list.size(), 0);
+    int32_t failed = -1;
+    { int32_t rc = exact_launch(h, spans.data(), (int32_t)list.size(), cov.data(), &failed); if (rc) return rc; }
+    if (failed >= 0)
+        return fail(h, PISCES_E_INVALID_ARG, "flush: Invalid indices -1--1: a read of several directions has no base at or before " + std::to_string(spans[2 * (size_t)failed]) +
+                                                 " and none at or behind " + std::to_string(spans[2 * (size_t)failed + 1]) + " (allele at position " +
+                                                 std::to_string(list[(size_t)failed]->position) + "); the reference throws here");
+    return PISCES_OK;
 }
 
 static bool owned(const PiscesHip* h, int32_t position) { return position >= h->own_lo && position <= h->own_hi; }   // (interval sharding: pisces_hip_set_owned_range)
@@ -1495,12 +1523,44 @@ static void span_collapse(SpanBatch& B, int64_t* n_collapsed)
 {
     PiscesHip* h = B.h;
     const int32_t stitched = h->cfg.expect_stitched_reads;
+    // CoverageMethod.Exact: the collapser's frequencies come from the same calculator (Factory.cs:130,184-185, VariantCollapser.cs:200-209).  A
+    // spanning allele's coverage depends on its span alone, and the collapser asks for members of B.work only, whose position and alleles a
+    // collapse does not change (collapse_candidates adds support and narrows the open ends): one launch over the batch ahead of the collapse
+    // serves every look-up, also of a target that has taken another allele's support since
+    std::map<std::pair<int32_t, int32_t>, int32_t> exact_total;
+    auto exact_lookup = [&](const HostCandidate& c, int32_t* total) {
+        int32_t span[2];
+        exact_span_of(c, span);
+        if (span[0] > span[1]) return false;
+        auto it = exact_total.find({span[0], span[1]});
+        if (it == exact_total.end()) {   // (cannot be: every member of the batch was counted below)
+            if (B.exact_rc == PISCES_OK) B.exact_rc = fail(h, PISCES_E_INTERNAL, "flush: the collapser asked for the exact coverage of a span that is not among the batch's own");
+            *total = 0;
+            return true;
+        }
+        *total = it->second;
+        return true;
+    };
+    if (h->exact_on) {
+        std::vector<const HostCandidate*> list;
+        for (auto& c : B.work)
+            if (c.category != PISCES_CAT_SNV && c.category != PISCES_CAT_REFERENCE) list.push_back(&c);
+        std::vector<int32_t> cov;
+        B.exact_rc = exact_candidate_coverage(h, list, cov);
+        if (B.exact_rc) return;
+        for (size_t i = 0; i < list.size(); i++) {
+            int32_t span[2];
+            exact_span_of(*list[i], span);
+            exact_total[{span[0], span[1]}] = cov[4 * i] + cov[4 * i + 1] + cov[4 * i + 2];
+        }
+    }
     *n_collapsed = collapse_candidates(B.work, h->cfg.collapse_freq_threshold, h->cfg.collapse_freq_ratio_threshold, [&](const HostCandidate& c) {
         DevCandidate d;
         to_dev(B, c, d);
         d.start_idx = row_index(B, d.start_idx);   // (rows of the gathered loci, not of the tensor)
         d.end_idx = row_index(B, d.end_idx);
-        const int total = candidate_total_coverage(d, B.host_counts, stitched);
+        int total = 0;
+        if (!h->exact_on || !exact_lookup(c, &total)) total = candidate_total_coverage(d, B.host_counts, stitched);
         const int support = c.support_by_dir[0] + c.support_by_dir[1] + c.support_by_dir[2];
         if (total == 0) return 0.0f;                       // CalledAllele.Frequency (CalledAllele.cs:49-52)
         const float f = (float)support / (float)total;
@@ -1592,9 +1652,14 @@ static int32_t span_device_pass(SpanBatch& B, const std::vector<const HostCandid
     // waits for it)
     { int32_t rcu = meta_upload(h, h->d_cands.p, dc.data(), dc.size() * sizeof(DevCandidate)); if (rcu) return rcu; }
     { int32_t rcu = meta_upload(h, h->d_alleles.p, pool.data(), pool.size()); if (rcu) return rcu; }
+    if (h->exact_on) {   // CoverageMethod.Exact: the table parallel to d_cands, one launch ahead of the pass that reads it
+        std::vector<int32_t> cov;
+        int32_t rcx = exact_candidate_coverage(h, list, cov);
+        if (rcx) return rcx;
+    }
     hipLaunchKernelGGL(call_spanning_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, h->stream, h->d_cands.p, n, h->d_counts.p,
                        h->d_alleles.p, h->d_ref.p, h->ref_len, h->cfg.expect_stitched_reads, h->d_cand_records.p, h->d_cand_callable.p, h->P,
-                       window ? h->d_sumq.p : (const double*)nullptr, B.d_folded, wanted);
+                       window ? h->d_sumq.p : (const double*)nullptr, B.d_folded, wanted, h->exact_on ? (const int32_t*)h->d_exact_out.p : (const int32_t*)nullptr);
     PISCES_HIP_CHECK(h, hipGetLastError());
     const size_t rec_bytes = wanted == kSpanningFlagsOnly ? 0 : B.raw.size() * sizeof(PiscesCalledAllele), need = rec_bytes + B.callable.size();
     h->pcie[1] += (int64_t)need;
@@ -1823,6 +1888,7 @@ static int32_t call_spanning(PiscesHip* h, const std::vector<int32_t>& keys, int
     phase(3);
     if (h->cfg.collapse) {
         span_collapse(B, n_collapsed);
+        if (B.exact_rc) return B.exact_rc;
         if (B.max_cleared >= 0 && B.work.empty() && B.unw.empty()) return PISCES_OK;
     }
     if (!B.unw.empty()) {

@@ -112,6 +112,7 @@ int32_t pisces_hip_add_observations(PiscesHip* h, const int32_t* positions, cons
     if (!h) return PISCES_E_INVALID_ARG;
     if (n < 0 || (n > 0 && (!positions || !tuples))) return fail(h, PISCES_E_INVALID_ARG, "add_observations: null buffer");
     if (h->amp_on) return fail(h, PISCES_E_UNSUPPORTED, "add_observations: the handle tracks amplicon counts (pisces_hip_set_amplicon_bias_filter): observation tuples have no read identity");
+    if (h->exact_on) return fail(h, PISCES_E_UNSUPPORTED, "add_observations: the handle counts spanning reads (pisces_hip_set_coverage_method, Exact): observation tuples have no reads");
     for (int64_t i = 0; i < n; i++)
         if (positions[i] <= 0) return fail(h, PISCES_E_INVALID_ARG, "Position must be greater than 0.");  // RegionStateManager.cs:363-364
     { int32_t rcp = refuse_while_batch_is_open(h, "add_observations"); if (rcp) return rcp; }
@@ -292,6 +293,7 @@ int32_t pisces_hip_set_forced_alleles(PiscesHip* h, const PiscesCandidate* cands
     if (!h) return PISCES_E_INVALID_ARG;
     if (h->n_forced_added > 0) return fail(h, PISCES_E_INVALID_ARG, "set_forced_alleles: some forced alleles are candidates already");
     if (h->amp_on) return fail(h, PISCES_E_UNSUPPORTED, "set_forced_alleles: the handle tracks amplicon counts (pisces_hip_set_amplicon_bias_filter): a forced allele has no support by amplicon");
+    if (h->exact_on && n > 0) return fail(h, PISCES_E_UNSUPPORTED, "set_forced_alleles: the handle counts spanning reads (pisces_hip_set_coverage_method, Exact): forced alleles are not carried through the Exact calculator");
     std::vector<HostCandidate> list;
     int32_t rc = host_candidates_of(h, cands, n, alleles, allele_bytes, list, "set_forced_alleles");
     if (rc) return rc;

@@ -649,6 +649,80 @@ static int32_t amplicon_launch(PiscesHip* h, const char* what, const PiscesTile*
     return PISCES_OK;
 }
 
+// An exact handle (pisces_hip_set_coverage_method): the coverage summaries of the batch that is about to join segment g, behind the ones the
+// segment holds (exact_summary_kernel, one lane a read, from the batch's own arrays), the segment's two search bounds and — the handle's first
+// read — RegionStateManager._readLength.  extra_keys: the blocks that exist only because a read's clip-adjusted END lies in them
+// (AddReadSummary's GetBlock, RegionStateManager.cs:216), ascending; the caller makes them and lets them hold the segment.  One wait: a word
+// that says whether the batch has any (a trailing soft clip across a block's edge: rare), and then a key per read.
+static int32_t exact_store_summaries(PiscesHip* h, ReadSegment& g, const StoreBatchArrays& A, int32_t nr, size_t n_cig, std::vector<int32_t>* extra_keys)
+{
+    extra_keys->clear();
+    if (nr <= 0) return PISCES_OK;
+    const size_t n0 = (size_t)g.n_reads;
+    PISCES_HIP_CHECK(h, g.x_sum.grow_keep(n0 + (size_t)nr, n0, h->stream));
+    PISCES_HIP_CHECK(h, g.x_bounds.reserve(2));
+    PISCES_HIP_CHECK(h, h->d_exact_words.reserve(4));
+    PISCES_HIP_CHECK(h, h->d_exact_extra.reserve((size_t)nr));
+    if (n0 == 0) PISCES_HIP_CHECK(h, hipMemsetAsync(g.x_bounds.p, 0, 2 * sizeof(int32_t), h->stream));   // (a segment's buffers are reused)
+    if (!h->exact_l0_set) PISCES_HIP_CHECK(h, hipMemsetD32Async((hipDeviceptr_t)h->d_exact_words.p, -1, 1, h->stream));
+    PISCES_HIP_CHECK(h, hipMemsetAsync(h->d_exact_words.p + 1, 0, sizeof(int32_t), h->stream));
+    hipLaunchKernelGGL(exact_summary_kernel, dim3((unsigned)((nr + 255) / 256)), dim3(256), 0, h->stream, A.position, A.flags, A.cigar_offset, A.cigar_op, A.cigar_len,
+                       A.seq_offset, A.dirs, nr, (int32_t)n_cig, h->cfg.block_size, g.x_sum.p + n0, g.x_bounds.p, h->exact_l0_set ? (int32_t*)nullptr : h->d_exact_words.p,
+                       h->d_exact_extra.p, h->d_exact_words.p + 1);
+    PISCES_HIP_CHECK(h, hipGetLastError());
+    int32_t any = 0;
+    PISCES_HIP_CHECK(h, hipMemcpyAsync(&any, h->d_exact_words.p + 1, sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    PISCES_HIP_CHECK(h, hipStreamSynchronize(h->stream));
+    // (exact_l0_set is the caller's to latch, once the batch is committed: a refused batch leaves no read length behind)
+    if (any) {
+        std::vector<int32_t> keys((size_t)nr);
+        PISCES_HIP_CHECK(h, hipMemcpy(keys.data(), h->d_exact_extra.p, (size_t)nr * sizeof(int32_t), hipMemcpyDeviceToHost));
+        for (int32_t k : keys)
+            if (k > 0) extra_keys->push_back(k);
+        std::sort(extra_keys->begin(), extra_keys->end());
+        extra_keys->erase(std::unique(extra_keys->begin(), extra_keys->end()), extra_keys->end());
+    }
+    return PISCES_OK;
+}
+static void exact_view(PiscesHip* h, ExactView* X)
+{
+    std::memset(X, 0, sizeof(*X));
+    int n = 0;
+    for (auto& sp : h->segments) {   // (store_view's order and its skips)
+        if (sp->n_reads == 0 || n == kMaxSegments) continue;
+        X->sum[n] = sp->x_sum.p;
+        X->bounds[n] = sp->x_bounds.p;
+        n++;
+    }
+}
+// exact_span_kernel over n spans ({preceding, trailing} each; preceding > trailing: no spanning allele, zeros): out[4 n] = the three counts and
+// the error word of every span.  Waits for the launch.  *failed: index of the lowest span at which a read ran into the reference's
+// InvalidDataException (exact_span.h kNoIndices), -1 when none did.
+static int32_t exact_launch(PiscesHip* h, const int32_t* spans, int32_t n, int32_t* out, int32_t* failed)
+{
+    *failed = -1;
+    if (n <= 0) return PISCES_OK;
+    StoreView V;
+    store_view(h, &V);
+    ExactView X;
+    exact_view(h, &X);
+    PISCES_HIP_CHECK(h, h->d_exact_words.reserve(4));
+    PISCES_HIP_CHECK(h, h->d_exact_spans.reserve(2 * (size_t)n));
+    PISCES_HIP_CHECK(h, h->d_exact_out.reserve(4 * (size_t)n));
+    if (!h->exact_l0_set) PISCES_HIP_CHECK(h, hipMemsetD32Async((hipDeviceptr_t)h->d_exact_words.p, -1, 1, h->stream));   // (no read yet: nothing is seen)
+    PISCES_HIP_CHECK(h, hipMemsetD32Async((hipDeviceptr_t)(h->d_exact_words.p + 2), kExactNoError, 1, h->stream));
+    PISCES_HIP_CHECK(h, hipMemcpyAsync(h->d_exact_spans.p, spans, 2 * (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+    hipLaunchKernelGGL(exact_span_kernel, dim3((unsigned)n), dim3(64), 0, h->stream, V, X, (const int32_t*)h->d_exact_spans.p, n, (const int32_t*)h->d_exact_words.p,
+                       h->d_exact_out.p, h->d_exact_words.p + 2);
+    PISCES_HIP_CHECK(h, hipGetLastError());
+    int32_t err = kExactNoError;
+    PISCES_HIP_CHECK(h, hipMemcpyAsync(out, h->d_exact_out.p, 4 * (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    PISCES_HIP_CHECK(h, hipMemcpyAsync(&err, h->d_exact_words.p + 2, sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    PISCES_HIP_CHECK(h, hipStreamSynchronize(h->stream));
+    if (err != kExactNoError) *failed = err;
+    return PISCES_OK;
+}
+
 // The tail of every add into the read store, once the batch's arrays lie on the device at d and its checks are in (rc_in: their verdict):
 // descriptors and fragments (read_shape_kernel), candidate discovery, and — only now — the handle's state.  fslots_host: the candidate-record
 // slots the host pass made (uploaded here), or nullptr when they were made on the device.
@@ -686,6 +760,11 @@ static int32_t store_finish_add(PiscesHip* h, StorePlace& pl, int32_t rc, uint8_
         h->found.min_position = min_position;   // (a flush up to a position below every read of this batch need not wait for its candidates)
     }
     if (rc == PISCES_OK && h->amp_on) rc = amplicon_store_ids(h, *pl.seg, db.cigar_offset, nr, n_cig);
+    std::vector<int32_t> exact_keys;   // an exact handle: the blocks of the reads' clip-adjusted ends that no aligned base touches
+    if (rc == PISCES_OK && h->exact_on) {
+        const StoreBatchArrays A = {db.position, db.flags, db.cigar_offset, db.cigar_op, db.cigar_len, db.seq_offset, db.bases, db.quals, db.dirs};
+        rc = exact_store_summaries(h, *pl.seg, A, nr, n_cig, &exact_keys);
+    }
     { int32_t rcs = stage_release(h); if (rc == PISCES_OK) rc = rcs; }   // (transfers out of the pinned buffer may be in flight whatever happened after them)
     if (rc) {
         (void)store_run_deferred(h);   // (before the segment's buffers can go)
@@ -706,8 +785,11 @@ static int32_t store_finish_add(PiscesHip* h, StorePlace& pl, int32_t rc, uint8_
     g.n_bases += (int64_t)n_seq;
     g.n_ops += (int64_t)n_cig;
     g.max_key = std::max(g.max_key, max_key);
+    if (!exact_keys.empty()) g.max_key = std::max(g.max_key, exact_keys.back());
+    if (h->exact_on && nr > 0) h->exact_l0_set = true;
     store_maybe_seal(h, &g);
     for (int32_t k : touched) (void)get_block(h, (k - 1) * bs + 1);
+    for (int32_t k : exact_keys) (void)get_block(h, (k - 1) * bs + 1);
     h->stats[2] += nr;
     return PISCES_OK;
 }
@@ -977,6 +1059,8 @@ static int32_t add_decoded_reads_store(PiscesHip* h, int64_t found_slots, int64_
         rc = enqueue_candidate_discovery(h, db, B.has_dirs ? B.del_dirs.p : nullptr, nr, (const int32_t*)B.d_fslots.p, found_slots, found_pool);
     }
     if (rc == PISCES_OK && h->amp_on) rc = amplicon_store_ids(h, g, A.cigar_offset, nr, n_cig);
+    std::vector<int32_t> exact_keys;
+    if (rc == PISCES_OK && h->exact_on) rc = exact_store_summaries(h, g, A, nr, n_cig, &exact_keys);
     if (rc) {
         (void)hipStreamSynchronize(h->stream);
         if (pl.direct) { g.bases.swap(B.bases); g.quals.swap(B.quals); g.cop.swap(B.cigar_op); g.clen.swap(B.cigar_len); if (B.has_dirs) g.dirs.swap(B.dirs); B.moved = false; }
@@ -987,6 +1071,9 @@ static int32_t add_decoded_reads_store(PiscesHip* h, int64_t found_slots, int64_
     g.n_bases += (int64_t)n_seq;
     g.n_ops += (int64_t)n_cig;
     g.max_key = std::max(g.max_key, max_key);
+    if (!exact_keys.empty()) g.max_key = std::max(g.max_key, exact_keys.back());
+    if (h->exact_on && nr > 0) h->exact_l0_set = true;
+    for (int32_t k : exact_keys) (void)get_block(h, (k - 1) * h->cfg.block_size + 1);
     store_maybe_seal(h, &g);
     return PISCES_OK;
 }

@@ -114,6 +114,27 @@ class HipVariantCaller:
         """pisces_hip_set_owned_range: the positions this shard owns (candidates of its halo reads outside them are the neighbour's)."""
         _check(self._h, lib.pisces_hip_set_owned_range(self._h, int(lo), int(hi)))
 
+    def SetCoverageMethod(self, method):
+        """PiscesApplicationOptions.CoverageMethod: "approximate" / "exact" (or _abi.COVERAGE_*), before the first read is added.  An exact
+        handle counts the reads that span every insertion, deletion and MNV of a flush (ExactCoverageCalculator) from the read store."""
+        if isinstance(method, str):
+            names = {"approximate": _abi.COVERAGE_APPROXIMATE, "exact": _abi.COVERAGE_EXACT}
+            if method.lower() not in names:
+                raise PiscesHipError(_abi.E_INVALID_ARG, f"SetCoverageMethod: {method!r} is no CoverageMethod")
+            method = names[method.lower()]
+        _check(self._h, lib.pisces_hip_set_coverage_method(self._h, int(method)))
+
+    set_coverage_method = SetCoverageMethod
+
+    def GetSpanningReadCounts(self, preceding, trailing, is_insertion=False):
+        """What ExactCoverageCalculator needs of IAlleleSource.GetSpanningReadSummaries(preceding, trailing): the reads the store holds that
+        span the two positions, by direction (int32[3]).  An exact handle only."""
+        out = (C.c_int32 * 3)()
+        _check(self._h, lib.pisces_hip_get_spanning_read_counts(self._h, int(preceding), int(trailing), int(bool(is_insertion)), out))
+        return np.array(list(out), dtype=np.int32)
+
+    spanning_read_counts = GetSpanningReadCounts
+
     # ---- IStateManager ----
     def SetAmpliconBiasFilter(self, threshold):
         """VariantCallingParameters.AmpliconBiasFilterThreshold (None = off): before the first read is added."""
@@ -799,6 +820,36 @@ def amplicon_bias(support, coverage, threshold):
     rc = lib.pisces_hip_amplicon_bias(sup.ctypes.data_as(i32p), cov.ctypes.data_as(i32p), len(sup), float(threshold),
                                       chance.ctypes.data_as(C.POINTER(C.c_double)))
     return (None, None) if rc < 0 else (bool(rc), chance)
+
+
+_CIGAR_RE = None
+
+
+def exact_span_direction(cs, ce, cigar, directions, preceding, trailing, is_insertion=False):
+    """pisces_hip_exact_span_direction for one read's coverage summary: cigar a string ("5M4I4M") or [(op, length)], directions the
+    reference's direction string ("2F:9S:2R") or [(DIR_*, length)].  Returns 0 / 1 / 2, None when the read does not span [preceding,
+    trailing]; raises where the reference throws (-2) or would index out of bounds (-3: runs longer than the read)."""
+    global _CIGAR_RE
+    if isinstance(cigar, str):
+        import re
+        _CIGAR_RE = _CIGAR_RE or re.compile(r"(\d+)([A-Za-z=])")
+        cigar = [(m.group(2), int(m.group(1))) for m in _CIGAR_RE.finditer(cigar)]
+    if isinstance(directions, str):
+        directions = [("FRS".index(tok[-1]), int(tok[:-1])) for tok in directions.split(":") if tok]
+    ops = np.array([ord(o) if isinstance(o, str) else int(o) for o, _ in cigar], dtype=np.uint8)
+    lens = np.array([n for _, n in cigar], dtype=np.uint32)
+    rt = np.array([d for d, _ in directions], dtype=np.uint8)
+    rl = np.array([n for _, n in directions], dtype=np.uint32)
+    rc = lib.pisces_hip_exact_span_direction(int(cs), int(ce), ops.ctypes.data, lens.ctypes.data, len(ops), rt.ctypes.data, rl.ctypes.data, len(rt),
+                                             int(preceding), int(trailing), int(bool(is_insertion)))
+    if rc == -1:
+        return None
+    if rc == -2:
+        raise PiscesHipError(_abi.E_INVALID_ARG, "exact_span_direction: Invalid indices -1--1 (the reference throws InvalidDataException)")
+    if rc < 0:
+        raise PiscesHipError(_abi.E_INVALID_ARG, "exact_span_direction: arguments the reference would index out of bounds with: direction runs longer than "
+                                                 "the CIGAR's read span, a direction above 2, or a missing array")
+    return rc
 
 
 def new_pad_state():
