@@ -726,8 +726,9 @@ __device__ inline int rmxn_run(const uint8_t* ref, int64_t lo, int64_t hi, int64
 __device__ inline bool rmxn_should_filter_snv(const uint8_t* ref, int64_t win_lo, int64_t win_hi, int32_t position,
                                               uint8_t refBase, uint8_t altBase, float freq, const DeviceParams& P)
 {
-    if (P.rmxn_max_len < 1) return false;   // a one-base unit needs maxRepeatUnitLength >= 1
+    if (P.rmxn_max_len < 0) return false;   // off
     if (freq >= P.rmxn_freq_limit) return false;
+    if (P.rmxn_max_len == 0) return 0 >= P.rmxn_min_rep;   // no bookends (a one-base unit needs maxRepeatUnitLength >= 1): every component is 0
     // string index of `position` is position-1
     int c1 = rmxn_run(ref, win_lo, win_hi, (int64_t)position - 1, refBase);
     int i1 = rmxn_run(ref, win_lo, win_hi, (int64_t)position, altBase);      // ReferencePosition + refLen - 1
@@ -752,8 +753,9 @@ __device__ inline int rmxn_run_lds(const uint8_t* win, int n, int start, uint8_t
 __device__ inline bool rmxn_should_filter_snv_lds(const uint8_t* win, int n, int idx /* window index of the SNV */,
                                                   uint8_t refBase, uint8_t altBase, float freq, const DeviceParams& P)
 {
-    if (P.rmxn_max_len < 1) return false;
+    if (P.rmxn_max_len < 0) return false;
     if (freq >= P.rmxn_freq_limit) return false;
+    if (P.rmxn_max_len == 0) return 0 >= P.rmxn_min_rep;
     // min(c1, c2) >= m  <=>  c1 >= m and c2 >= m: the reference-base run decides first, and almost always at once.  Its eight
     // neighbours are read together (one LDS round trip instead of a dependent chain); a run that stays inside them is exact.
     if (idx >= 4 && idx + 4 < n) {
