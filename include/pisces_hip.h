@@ -83,8 +83,11 @@ enum { PISCES_PLOIDY_SOMATIC = 0, PISCES_PLOIDY_DIPLOID = 1, PISCES_PLOIDY_HAPLO
  * bit 24..31  base quality (deletion tuples carry 255: their quality gate,
  *             CheckDeletionQuality, was applied when the read was expanded)
  * The kernel applies "qual < minBQ -> N" (RegionStateManager.cs:179-181).
- * A tile has at most 64 loci, so every column value is a locus of the tile: no tuple can address memory outside its
- * tile's histogram; allele codes 6, 7 and direction 3 select rows nobody reads. */
+ * A tile has at most 64 loci and the column has six bits, so no tuple can address memory outside its tile's histogram.
+ * Tuples that count for nothing, in every kernel that takes tuples (tests/test_tuple_geometry_gpu.py): a locus at or beyond
+ * the tile's n_loci (a tile may have fewer than 64 loci; the column of such a locus is a counter nobody reads), allele codes
+ * 6, 7 and direction 3 (rows nobody reads), an anchor code of 11..15 (there is no such bin: it adds 0), and the pad word.
+ * Bits 0..1 and 17..23 must be zero as stated: the hot kernel tells a valid anchor by a carry out of bit 16. */
 #define PISCES_TUPLE_MAX_TILE   64
 #define PISCES_TUPLE_COLUMN(locus, dir) \
     (((((uint32_t)(locus) >> 2) & 15u) | (((uint32_t)(locus) & 3u) << 4)) ^ (((uint32_t)(dir) & 1u) << 4))

@@ -2682,6 +2682,9 @@ int64_t orc_run_observations(const int32_t* positions, const uint32_t* tuples, i
         /* RegionStateManager.cs:179-181 */
         if (allele < PISCES_ALLELE_N && qual < cfg->min_base_call_quality) allele = PISCES_ALLELE_N;
         add_allele_count(s, pos, allele, dir, anchor);
+        /* NoiseModel.Window: the base's quality under its post-threshold allele type, Math.Pow(10, -1 * (int)q / 10f) :191
+         * (a deletion tuple is no base: its 255 is a marker, and only A / C / G / T sums are ever read, CoverageCalculator.cs:62) */
+        if (allele != PISCES_ALLELE_DEL) add_base_quality(s, pos, allele, dir, pow(10.0, (double)((float)(-1 * qual) / 10.0f)), anchor);
         /* the SNV candidate this observation implies (CandidateVariantFinder.cs:97-160, callMNVs off) */
         if (in_region(s, pos) && allele < PISCES_ALLELE_N && pos <= ref_len) {
             uint8_t rb = ref_bases[pos - 1];

@@ -1,7 +1,7 @@
 // kernels.hip.h — gfx950 kernels of the pileup-and-likelihood path.
 //
 //   call_tiles_wave_kernel<NW>  THE HOT KERNEL: one tile (<= 64 loci) per wave, NW waves per workgroup.  Observation tuples stream in
-//                            as 16-byte loads; the tuple IS the LDS address of its counter (3 VALU + 1 ds_add per observation, two
+//                            as 16-byte loads; the tuple IS the LDS address of its counter (5 VALU + 1 ds_add per observation, two
 //                            [32][64] int32 regions: quality-passing / low-quality bases); the call phase — coverage, Poisson
 //                            q-score, strand bias, somatic genotype, filters for the Reference allele and every SNV candidate —
 //                            reads memo tables first (DeviceParams::vq_tab / sb_tab / gq_cap, filled by the functions they stand for)
@@ -62,7 +62,8 @@ __device__ __forceinline__ int allele_type_of_base(uint8_t c)  // AlleleHelper.G
 
 // One observation into the folded LDS histogram hist[(allele*3+dir)*kTile + locus].
 // "qual < minBQ -> N" is RegionStateManager.cs:179-181; deletion tuples carry qual 255.
-// Padding tuples (0xFFFFFFFF) decode to allele 7 and fall out of the range test.
+// Padding tuples (0xFFFFFFFF) decode to allele 7 and fall out of the range test; an anchor code beyond the bins counts for nothing here
+// as it does where the bins are kept (accumulate_tiles_kernel).
 __device__ __forceinline__ void accumulate_folded(int* hist, uint32_t t, uint32_t n_loci, uint32_t min_bq)
 {
     uint32_t locus = PISCES_TUPLE_LOCUS(t);
@@ -70,20 +71,27 @@ __device__ __forceinline__ void accumulate_folded(int* hist, uint32_t t, uint32_
     uint32_t allele = PISCES_TUPLE_ALLELE(t);
     uint32_t qual = PISCES_TUPLE_QUAL(t);
     if (allele < 4u && qual < min_bq) allele = 4u;
-    if (locus < n_loci && dir < 3u && allele < 6u) atomicAdd(&hist[(allele * 3u + dir) * kTile + locus], 1);
+    if (locus < n_loci && dir < 3u && allele < 6u && PISCES_TUPLE_ANCHOR(t) < (uint32_t)PISCES_NUM_ANCHORS)
+        atomicAdd(&hist[(allele * 3u + dir) * kTile + locus], 1);
 }
 
 // Wave-kernel form.  The tuple is laid out for this (include/pisces_hip.h): bits 2..12 ARE the byte offset of the (allele, direction,
-// column) counter in a [32][64] int32 region, so an observation is 3 VALU + 1 DS instruction: one compare-and-select for "qual <
+// column) counter in a [32][64] int32 region, so an observation is 5 VALU + 1 DS instruction: one compare-and-select for "qual <
 // minBQ" (RegionStateManager.cs:179-181; it picks the second region, whose counts the call phase adds to N, or to the deletion
-// count for a deletion tuple, exactly where the remapped allele would have gone), one and-or for the address, ds_add_u32.  No
-// branch, no exec masking, no range test: six column bits cannot leave the tile, padding tuples (all ones) and invalid allele /
-// direction codes select rows nobody reads.
+// count for a deletion tuple, exactly where the remapped allele would have gone), one and-or for the address, an add and a bit-field
+// extract for what is added, ds_add_u32.  No branch, no exec masking, no range test: six column bits cannot leave the tile (a column
+// at or beyond the tile's n_loci is a counter the call phase does not read), padding tuples (all ones) and invalid allele /
+// direction codes select rows nobody reads.  The anchor is the one field the rows do not carry: a code of 11..15 (no such bin; the
+// kernels that keep the bins drop it) adds 0 where a bin adds 1.  Bits 17..23 of a tuple are zero, so bit 17 of
+// t + ((32 - PISCES_NUM_ANCHORS) << 13) is "anchor < PISCES_NUM_ANCHORS": anchor + 21 is 21..31 for a bin and 32..36 for a code of
+// 11..15, which carries into bit 18 and clears bit 17.  (One add whose carry-out is also the quality test, in place of the compare,
+// measured slower: 40.5 us a config-2 launch against 40.3 for this form and 40.0 without the anchor test)
 __device__ __forceinline__ void accumulate_wave(int* hist, uint32_t t, uint32_t min_bq_shifted)
 {
     const uint32_t region = (t < min_bq_shifted) ? (uint32_t)(kWaveRegion * sizeof(int)) : 0u;   // qual is the top byte: qual < minBQ <=> t < minBQ << 24
     const uint32_t off = (t & 0x1FFCu) | region;
-    atomicAdd(reinterpret_cast<int*>(reinterpret_cast<char*>(hist) + off), 1);
+    const uint32_t one = ((t + ((32u - (uint32_t)PISCES_NUM_ANCHORS) << 13)) >> 17) & 1u;
+    atomicAdd(reinterpret_cast<int*>(reinterpret_cast<char*>(hist) + off), (int)one);
 }
 
 // Streams tuples[begin, end) through `op(tuple)`: scalar head/tail up to 16-byte alignment, then

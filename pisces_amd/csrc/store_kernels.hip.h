@@ -1610,7 +1610,7 @@ __global__ __launch_bounds__(64 * NW, NW == 1 ? PISCES_WAVE_OCC : PISCES_WAVE2_O
     for (int64_t i = tile.tuple_begin + threadIdx.x; i < tile.tuple_end; i += 64 * NW) {
         const uint32_t v = tuples[i];
         const uint32_t dir = PISCES_TUPLE_DIR(v), allele = PISCES_TUPLE_ALLELE(v);
-        if (dir < 3u && allele < 6u)
+        if (dir < 3u && allele < 6u && PISCES_TUPLE_ANCHOR(v) < (uint32_t)PISCES_NUM_ANCHORS)
             atomicAdd(reinterpret_cast<int*>(hbytes + ((PISCES_TUPLE_QUAL(v) < min_bq) ? kRegionBytes : 0u) +
                                              (uint32_t)HistLinear::idx((int)allele, (int)dir, (int)PISCES_TUPLE_LOCUS(v)) * (uint32_t)sizeof(int)), 1);
     }
