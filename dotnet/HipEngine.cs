@@ -451,6 +451,35 @@ namespace Pisces.Hip
             return counts;
         }
 
+        /// VCF body lines of device-resident rows, written on the device (pisces_hip_format_vcf_device) and handed to the writer's stream:
+        /// the text VcfFileWriter.WriteListOfColocatedAlleles produces for the same alleles, one line an allele (AllowMultipleVcfLinesPerLoci).
+        /// dRecords / dCount are what pisces_hip_compact_records left (dCount may be IntPtr.Zero: n rows), dPosteriors the compacted
+        /// posteriors or IntPtr.Zero.  dCandIndex / dCands / dAlleles are what pisces_hip_flush_ex returns, in device memory, for rows that
+        /// are insertions, deletions or MNVs; all three IntPtr.Zero when every row is a Reference or SNV row (a row without a candidate
+        /// prints the single-base alleles of its record).  text / textBytes are pinned host memory the device can write (capacity bytes
+        /// and one long).  The launches go to the HANDLE's stream, behind the pisces_hip_call_tiles / pisces_hip_compact_records calls
+        /// made with stream IntPtr.Zero, and pisces_hip_synchronize — which waits for that stream — is the one wait before the size word
+        /// and the text are read.  (A host that launches on a stream of its own calls pisces_hip_format_vcf_device itself and waits for
+        /// that stream.)  Returns the bytes the text needs: above `capacity` nothing was written (call again with a larger buffer).
+        public long WriteVcfDevice(PiscesVcfConfig cfg, string chrom, IntPtr dRecords, long n, IntPtr dCount, IntPtr dCandIndex, IntPtr dCands, IntPtr dAlleles,
+                                   IntPtr dPosteriors, IntPtr text, long capacity, IntPtr textBytes, System.IO.Stream writer)
+        {
+            NativeMethods.Check(_h, NativeMethods.pisces_hip_format_vcf_device(_h, ref cfg, chrom, dRecords, n, dCount, dCandIndex, dCands, dAlleles, dPosteriors,
+                                                                               text, capacity, IntPtr.Zero, textBytes, IntPtr.Zero));
+            NativeMethods.Check(_h, NativeMethods.pisces_hip_synchronize(_h));   // the handle's stream: the one the launches above went to
+            long need = System.Runtime.InteropServices.Marshal.ReadInt64(textBytes);
+            if (need < 0) NativeMethods.Check(_h, (int)need);                     // a row the host formatter refuses too
+            if (need > capacity) return need;
+            var chunk = new byte[(int)Math.Min(need, 1 << 20)];
+            for (long done = 0; done < need; done += chunk.Length)
+            {
+                int k = (int)Math.Min(chunk.LongLength, need - done);
+                System.Runtime.InteropServices.Marshal.Copy(new IntPtr(text.ToInt64() + done), chunk, 0, k);
+                writer.Write(chunk, 0, k);
+            }
+            return need;
+        }
+
         /// one interval shard of a chromosome: calls and totals only inside [lo, hi] (the reads of the halo still feed the counts)
         public void SetOwnedRange(int lo, int hi) { NativeMethods.Check(_h, NativeMethods.pisces_hip_set_owned_range(_h, lo, hi)); }
 

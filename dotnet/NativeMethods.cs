@@ -225,6 +225,7 @@ namespace Pisces.Hip
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pisces_hip_posteriors_view(IntPtr handle, out PiscesGenotypePosteriors* rows, out long n);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pisces_hip_set_posteriors_buffer(IntPtr handle, IntPtr dPosteriors, long capacity);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pisces_hip_compact_posteriors(IntPtr handle, IntPtr dPosteriors, IntPtr dTileResults, int nTiles, IntPtr dOffsets, IntPtr dOut, int outCapacity, IntPtr stream);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pisces_hip_format_vcf_device(IntPtr handle, ref PiscesVcfConfig cfg, [MarshalAs(UnmanagedType.LPStr)] string chrom, IntPtr dRecords, long n, IntPtr dCount, IntPtr dCandIndex, IntPtr dCands, IntPtr dAlleles, IntPtr dPosteriors, IntPtr dText, long textCapacity, IntPtr dLineOffsets, IntPtr dTextBytes, IntPtr stream);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pisces_hip_set_genotypes_adaptive(ref PiscesHipConfig cfg, ref PiscesAdaptiveParams p, [In, Out] PiscesGenotypeAllele[] allelesOfOneLocus, int n, byte[] alleles, long alleleBytes, [Out] PiscesGenotypePosteriors[] posteriors);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pisces_hip_adaptive_genotype_qscore(ref PiscesAdaptiveParams p, int category, int isReference, int alleleSupport, int totalCoverage, out int categoryOut, out int qscoreOut, [Out] float[] gp3);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern long pisces_hip_format_vcf_ex(ref PiscesVcfConfig cfg, [MarshalAs(UnmanagedType.LPStr)] string chrom, PiscesCalledAllele[] records, long n, int[] candIndex, PiscesCandidate[] cands, byte[] alleles, [Out] byte[] text, long capacity, PiscesGenotypePosteriors[] gp);

@@ -564,6 +564,31 @@ int32_t pisces_hip_set_posteriors_buffer(PiscesHip* h, PiscesGenotypePosteriors*
 int32_t pisces_hip_compact_posteriors(PiscesHip* h, const PiscesGenotypePosteriors* d_posteriors, const PiscesTileResult* d_tile_results,
                                       int32_t n_tiles, const int32_t* d_offsets, PiscesGenotypePosteriors* d_out, int32_t out_capacity,
                                       void* stream);
+/* VCF body lines of device-resident rows, written on the device: the bytes pisces_hip_format_vcf_ex writes for the same rows (one line
+ * a row; see "VCF body lines" below for the columns and PiscesVcfConfig).  Asynchronous on `stream` and ordered behind whatever made
+ * the rows: pisces_hip_call_tiles -> pisces_hip_compact_records -> this, with no host wait in between.  Every d_* pointer is
+ * device-accessible (d_text may be pinned host memory).
+ *   d_count        optional: the word pisces_hip_compact_records leaves; min(n, *d_count) rows are formatted (NULL: n)
+ *   d_cand_index, d_cands, d_alleles
+ *                  optional: what pisces_hip_flush_ex returns, in device memory; a row without an index >= 0 takes its alleles from
+ *                  the base codes of `info`
+ *   d_gp           optional: d_gp[i] belongs to row i, a row with n > 0 gets the :GP column
+ *   d_line_offsets optional, rows + 1 entries: the byte offset of every line, then the total (written when the text is)
+ *   *d_text_bytes  the bytes of text.  Above text_capacity: no byte of d_text was written, repeat with a larger buffer.  Negative:
+ *                  the PISCES_E_* code pisces_hip_format_vcf_ex returns for these rows (a LowVariantQscore bit with
+ *                  variant_quality_filter < 0, an RMxN bit without its two numbers, a cand_index >= 0 without candidates: the lowest
+ *                  such row decides, PISCES_E_INVALID_ARG), and no text either.
+ * Calls of one handle share the handle's scratch (4 bytes a row): like every launch of this surface they must be stream-ordered with
+ * respect to each other — one stream, or serialised by the caller.  A call that has to grow the scratch waits first: for its stream, or
+ * for the whole device once the handle has seen a stream that is not its own.
+ * Refused at the call: null h / cfg / chrom / d_text_bytes or a negative size (PISCES_E_INVALID_ARG); cfg->crush (crushed lines merge
+ * the rows of a position) and RegionMapper's padding stay with the host formatter, as do a chrom above 1024 bytes and thresholds that
+ * ask for more than 7 VF decimals (PISCES_E_UNSUPPORTED, each with a message). */
+struct PiscesVcfConfig;   /* defined with the VCF entries below */
+int32_t pisces_hip_format_vcf_device(PiscesHip* h, const struct PiscesVcfConfig* cfg, const char* chrom, const PiscesCalledAllele* d_recs,
+                                     int64_t n, const int32_t* d_count, const int32_t* d_cand_index, const PiscesCandidate* d_cands,
+                                     const uint8_t* d_alleles, const PiscesGenotypePosteriors* d_gp, char* d_text,
+                                     int64_t text_capacity, int64_t* d_line_offsets, int64_t* d_text_bytes, void* stream);
 /* tuples -> anchor-resolved counts added into d_counts[n_tiles*tile_loci][6][3][11]
  * (the IAlleleSource view for host-side collapsing / spanning coverage). Asynchronous. */
 int32_t pisces_hip_accumulate_tiles(PiscesHip* h, const uint32_t* d_tuples, const PiscesTile* d_tiles,

@@ -29,6 +29,7 @@ EXPORTS = [
     "pisces_hip_get_amplicon_counts", "pisces_hip_bam_fetch_amplicons", "pisces_hip_amplicon_name_count", "pisces_hip_get_amplicon_name",
     "pisces_hip_intern_amplicon_name",
     "pisces_hip_exact_span_direction", "pisces_hip_set_coverage_method", "pisces_hip_get_spanning_read_counts",
+    "pisces_hip_format_vcf_device",
 ]
 
 
@@ -162,6 +163,7 @@ def _load():
         "pisces_hip_format_vcf_ex": (i64, [P(_abi.PiscesVcfConfig), C.c_char_p, vp, i64, vp, vp, vp, vp, i64, vp]),
         "pisces_hip_format_vcf_padded_ex": (i64, [P(_abi.PiscesVcfConfig), C.c_char_p, vp, i64, vp, vp, vp, vp, i64, vp, vp, i32,
                                                   P(_abi.PiscesVcfPadState), i32, vp, i64, vp]),
+        "pisces_hip_format_vcf_device": (i32, [vp, P(_abi.PiscesVcfConfig), C.c_char_p, vp, i64, vp, vp, vp, vp, vp, vp, i64, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(lib, name)   # AttributeError here = a declared symbol is not exported

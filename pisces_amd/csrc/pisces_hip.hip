@@ -40,6 +40,8 @@
 #include "finder_kernels.hip.h"
 #include "bgzf_kernels.hip.h"
 #include "bam_kernels.hip.h"
+#include "vcf_kernels.hip.h"
+#include "vcf_format.h"
 
 using namespace pisces;
 
@@ -617,6 +619,10 @@ struct PiscesHip {
     DeviceBuf<int32_t> d_counts;
     DeviceBuf<uint32_t> d_gapped;
     DeviceBuf<int32_t> d_count;
+    // pisces_hip_format_vcf_device: line lengths, chunk totals / offsets, {lowest refused row, go}
+    DeviceBuf<uint32_t> d_vcf_len;
+    DeviceBuf<int64_t> d_vcf_chunk;
+    DeviceBuf<unsigned long long> d_vcf_ctrl;
 };
 
 #define PISCES_HIP_CHECK(h, expr)                                                              \
@@ -1218,6 +1224,8 @@ int32_t pisces_hip_set_owned_range(PiscesHip* h, int32_t lo, int32_t hi)
 #include "surface_amplicon.inc.h"
 
 #include "surface_exact.inc.h"
+
+#include "surface_vcf.inc.h"
 
 int32_t pisces_hip_synchronize(PiscesHip* h)
 {

@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "../../include/pisces_hip.h"
+#include "vcf_format.h"
 
 namespace {
 
@@ -111,6 +112,14 @@ const char* map_genotype(int gt)   // VcfFormatter.MapGenotype :184-216
 
 }  // namespace
 
+// VcfFormatter.UpdateFrequencyFormat :52-64
+int pisces_vcf_frequency_decimals(const PiscesVcfConfig* cfg)
+{
+    int freq_decimals = sig_digits_of(cfg->min_frequency_threshold);
+    if (cfg->frequency_filter_threshold >= 0.0f) freq_decimals = std::max(freq_decimals, sig_digits_of(cfg->frequency_filter_threshold));
+    return freq_decimals;
+}
+
 extern "C" {
 
 int32_t pisces_hip_vcf_default_config(PiscesVcfConfig* c)
@@ -141,9 +150,7 @@ int64_t pisces_hip_format_vcf_padded_ex(const PiscesVcfConfig* cfg, const char* 
     if (!cfg || !chrom || n < 0 || (n > 0 && !recs) || capacity < 0 || (capacity > 0 && !out)) return PISCES_E_INVALID_ARG;
     const bool pad = state != nullptr;
     if (pad && (n_intervals < 0 || (n_intervals > 0 && (!interval_starts || !interval_ends)) || !ref_bases || ref_len < 0)) return PISCES_E_INVALID_ARG;
-    // VcfFormatter.UpdateFrequencyFormat :52-64
-    int freq_decimals = sig_digits_of(cfg->min_frequency_threshold);
-    if (cfg->frequency_filter_threshold >= 0.0f) freq_decimals = std::max(freq_decimals, sig_digits_of(cfg->frequency_filter_threshold));
+    const int freq_decimals = pisces_vcf_frequency_decimals(cfg);
     static const char kBase[6] = {'A', 'G', 'C', 'T', 'N', 'D'};
     std::string format = "GT:GQ:AD:DP:VF";
     if (cfg->output_strand_bias_and_noise_level) format += ":NL:SB";

@@ -580,6 +580,50 @@ class HipVariantCaller:
         _check(self._h, lib.pisces_hip_compact_posteriors(self._h, d_posteriors, d_tile_results, n_tiles, d_offsets, d_out, out_capacity,
                                                           self._stream_arg(stream)))
 
+    def format_vcf_device(self, chrom, d_recs, n, vcf_config=None, d_count=None, d_cand_index=None, d_cands=None, d_alleles=None, d_gp=None,
+                          capacity=None, line_offsets=False, stream=None, **overrides):
+        """pisces_hip_format_vcf_device: the VCF body lines of `n` (or min(n, *d_count)) device-resident rows, written on the device and
+        returned as bytes — what format_vcf returns for the same rows, encoded.  Every d_* is a torch tensor or a raw device address;
+        d_count is the word compact_records leaves, d_cand_index / d_cands / d_alleles what CallWithAlleles' candidates are in device
+        memory, d_gp the compacted posteriors (the :GP column).  vcf_config / overrides as format_vcf takes them (crush is refused).
+        The launches go to `stream` (None = the handle's own) behind whatever made the rows; the call then waits once, for the size
+        word, and repeats with a buffer of that size when `capacity` (default 128 bytes a row) was short.  line_offsets=True returns
+        (text, offsets) with the rows + 1 byte offsets of the lines as a numpy int64 array."""
+        import torch
+        cfg = vcf_config
+        if cfg is None:
+            cfg = _abi.PiscesVcfConfig()
+            _check(None, lib.pisces_hip_vcf_default_config(C.byref(cfg)))
+        for k, v in overrides.items():
+            setattr(cfg, k, v)
+        ptr = lambda t: None if t is None else (int(t.data_ptr()) if hasattr(t, "data_ptr") else int(t))
+        raw = self._stream_arg(stream)
+        ts = self.torch_stream() if raw is None else torch.cuda.ExternalStream(raw, device=torch.device("cuda", self.device))
+        dev = torch.device("cuda", self.device)
+        n = int(n)
+        cap = int(capacity) if capacity is not None else 128 * max(n, 1)
+        size_word = torch.zeros(1, dtype=torch.int64).pin_memory()   # the kernel's own store into pinned memory: one stream wait, no copy
+        with torch.cuda.stream(ts):
+            offs = torch.full((n + 1,), -1, dtype=torch.int64, device=dev) if line_offsets else None
+            for _ in range(2):
+                text = torch.empty(max(cap, 1), dtype=torch.uint8, device=dev)
+                _check(self._h, lib.pisces_hip_format_vcf_device(self._h, C.byref(cfg), chrom.encode(), ptr(d_recs), n, ptr(d_count), ptr(d_cand_index),
+                                                                 ptr(d_cands), ptr(d_alleles), ptr(d_gp), text.data_ptr(), cap, ptr(offs),
+                                                                 size_word.data_ptr(), ts.cuda_stream))
+                ts.synchronize()
+                need = int(size_word[0])
+                if need < 0:
+                    raise PiscesHipError(need, "format_vcf_device: a row the host formatter refuses too (a filter bit whose name the configuration "
+                                               "does not give, or a candidate index without candidates)")
+                if need <= cap:
+                    break
+                cap = need
+            out = bytes(text[:need].cpu().numpy().tobytes())
+            if line_offsets:
+                written = offs.cpu().numpy()
+                return out, written[written >= 0]   # the rows + 1 entries the kernels wrote: min(n, *d_count) lines, then the total
+            return out
+
     def accumulate_tiles(self, d_tuples, d_tiles, n_tiles, d_counts, stream=None):
         _check(self._h, lib.pisces_hip_accumulate_tiles(self._h, d_tuples, d_tiles, n_tiles, d_counts, self._stream_arg(stream)))
 
