@@ -230,6 +230,7 @@ namespace Pisces.Hip
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pisces_hip_adaptive_genotype_qscore(ref PiscesAdaptiveParams p, int category, int isReference, int alleleSupport, int totalCoverage, out int categoryOut, out int qscoreOut, [Out] float[] gp3);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern long pisces_hip_format_vcf_ex(ref PiscesVcfConfig cfg, [MarshalAs(UnmanagedType.LPStr)] string chrom, PiscesCalledAllele[] records, long n, int[] candIndex, PiscesCandidate[] cands, byte[] alleles, [Out] byte[] text, long capacity, PiscesGenotypePosteriors[] gp);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern long pisces_hip_format_vcf_padded_ex(ref PiscesVcfConfig cfg, [MarshalAs(UnmanagedType.LPStr)] string chrom, PiscesCalledAllele[] records, long n, int[] candIndex, PiscesCandidate[] cands, byte[] alleles, byte[] referenceBases, long refLen, int[] intervalStarts, int[] intervalEnds, int nIntervals, ref PiscesVcfPadState state, int finish, [Out] byte[] text, long capacity, PiscesGenotypePosteriors[] gp);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pisces_hip_vcf_pad_plan(PiscesCalledAllele[] records, long n, int crush, int[] intervalStarts, int[] intervalEnds, int nIntervals, ref PiscesVcfPadState stateIn, int finish, out long padRows, out long lines, out PiscesVcfPadState stateOut);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pisces_hip_diploid_genotype_qscore(int genotype, int totalCoverage, int alleleSupport, int minQscore, int maxQscore);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pisces_hip_set_amplicon_bias_filter(IntPtr handle, float threshold);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pisces_hip_add_reads_amplicons(IntPtr handle, ref PiscesReadBatch batch, int[] ampliconId);

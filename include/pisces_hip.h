@@ -790,6 +790,17 @@ int64_t pisces_hip_format_vcf_padded(const PiscesVcfConfig* cfg, const char* chr
                                      const uint8_t* ref_bases, int64_t ref_len, const int32_t* interval_starts,
                                      const int32_t* interval_ends, int32_t n_intervals, PiscesVcfPadState* state, int32_t finish,
                                      char* out, int64_t capacity);
+/* The padding of such a call without its text, for a caller that sizes buffers or splits a chromosome's rows into calls: the no-call
+ * rows and the lines (rows written, one per position with `crush`, plus the no-call rows) pisces_hip_format_vcf_padded would write for
+ * `recs` from *state_in, and the state it would leave (each output may be NULL).  Closed form over the interval table — a binary search
+ * and a prefix sum per written line, no walk over the positions of a gap — so it asks for what the closed form
+ * needs: intervals positive, sorted and disjoint (PISCES_E_INVALID_ARG otherwise), rows at positions >= 1 that do not descend, the
+ * first not below state_in->last_variant_position_written, and a state that zero-initialisation or the formatter produced: no negative
+ * word, no index below -1, no last_padded_position ahead of last_variant_position_written while intervals are uncleared
+ * (PISCES_E_UNSUPPORTED otherwise: the formatter itself still takes such input).  A finished state, (0, L, n - 1), pads nothing more. */
+int32_t pisces_hip_vcf_pad_plan(const PiscesCalledAllele* recs, int64_t n, int32_t crush, const int32_t* interval_starts,
+                                const int32_t* interval_ends, int32_t n_intervals, const PiscesVcfPadState* state_in, int32_t finish,
+                                int64_t* pad_rows, int64_t* lines, PiscesVcfPadState* state_out);
 /* The two entries above with CalledAllele.GenotypePosteriors: gp[i] belongs to recs[i] (NULL: exactly the bytes of the entries above).
  * A line whose first allele has gp.n > 0 gets ":GP" behind its FORMAT keys and the values, each "0.00", comma-joined, behind its sample
  * (VcfFormatter.cs:263-269; ShouldReportGp is on with DiploidByAdaptiveGT); RegionMapper's no-call rows have none. */

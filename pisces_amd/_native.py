@@ -24,7 +24,7 @@ EXPORTS = [
     "pisces_hip_flush_end_ex", "pisces_hip_device_count", "pisces_hip_flush_view", "pisces_hip_flush_end_view", "pisces_hip_transfer_bytes",
     "pisces_hip_add_device_reads", "pisces_hip_get_stream", "pisces_hip_comm_library", "pisces_hip_comm_ranks", "pisces_hip_set_known_variants", "pisces_hip_set_exclude_mnvs_from_collapsing", "pisces_hip_set_exact_total_called", "pisces_hip_reallocate_failed_mnvs", "pisces_hip_set_genotypes", "pisces_hip_diploid_genotype_qscore",
     "pisces_hip_adaptive_default_params", "pisces_hip_set_adaptive_params", "pisces_hip_get_posteriors", "pisces_hip_posteriors_view", "pisces_hip_set_posteriors_buffer",
-    "pisces_hip_compact_posteriors", "pisces_hip_set_genotypes_adaptive", "pisces_hip_adaptive_genotype_qscore", "pisces_hip_format_vcf_ex", "pisces_hip_format_vcf_padded_ex",
+    "pisces_hip_compact_posteriors", "pisces_hip_set_genotypes_adaptive", "pisces_hip_adaptive_genotype_qscore", "pisces_hip_format_vcf_ex", "pisces_hip_format_vcf_padded_ex", "pisces_hip_vcf_pad_plan",
     "pisces_hip_amplicon_bias", "pisces_hip_set_amplicon_bias_filter", "pisces_hip_add_reads_amplicons", "pisces_hip_add_device_reads_amplicons",
     "pisces_hip_get_amplicon_counts", "pisces_hip_bam_fetch_amplicons", "pisces_hip_amplicon_name_count", "pisces_hip_get_amplicon_name",
     "pisces_hip_intern_amplicon_name",
@@ -163,6 +163,7 @@ def _load():
         "pisces_hip_format_vcf_ex": (i64, [P(_abi.PiscesVcfConfig), C.c_char_p, vp, i64, vp, vp, vp, vp, i64, vp]),
         "pisces_hip_format_vcf_padded_ex": (i64, [P(_abi.PiscesVcfConfig), C.c_char_p, vp, i64, vp, vp, vp, vp, i64, vp, vp, i32,
                                                   P(_abi.PiscesVcfPadState), i32, vp, i64, vp]),
+        "pisces_hip_vcf_pad_plan": (i32, [vp, i64, i32, vp, vp, i32, P(_abi.PiscesVcfPadState), i32, P(i64), P(i64), P(_abi.PiscesVcfPadState)]),
         "pisces_hip_format_vcf_device": (i32, [vp, P(_abi.PiscesVcfConfig), C.c_char_p, vp, i64, vp, vp, vp, vp, vp, vp, i64, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():

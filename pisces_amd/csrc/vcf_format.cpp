@@ -7,6 +7,7 @@
 // decimal digits of the float (15 for Double), then rounds that digit string half-up to the requested decimals, and a negative
 // value that rounds to zero prints without the sign.
 #include <algorithm>
+#include <climits>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -359,6 +360,75 @@ int64_t pisces_hip_format_vcf_padded_ex(const PiscesVcfConfig* cfg, const char* 
     }
     return need;   // > capacity: nothing was written and the state is unchanged, call again with a buffer of this size
     }();
+    } catch (...) {
+        return PISCES_E_INTERNAL;
+    }
+}
+
+// The padding of a call without its text: what pisces_hip_format_vcf_padded_ex above does to the state and how many no-call rows it
+// writes, in closed form — per written line two binary searches over the interval table and a prefix sum of the
+// interval lengths, no walk over the positions of a gap.
+int32_t pisces_hip_vcf_pad_plan(const PiscesCalledAllele* recs, int64_t n, int32_t crush, const int32_t* interval_starts,
+                                const int32_t* interval_ends, int32_t n_intervals, const PiscesVcfPadState* state_in, int32_t finish,
+                                int64_t* pad_rows, int64_t* lines, PiscesVcfPadState* state_out)
+{
+    try {
+    if (n < 0 || (n > 0 && !recs) || n_intervals < 0 || (n_intervals > 0 && (!interval_starts || !interval_ends)) || !state_in) return PISCES_E_INVALID_ARG;
+    std::vector<int64_t> prefix((size_t)n_intervals + 1, 0);   // positions of the intervals in front of k
+    for (int32_t k = 0; k < n_intervals; k++) {
+        if (interval_starts[k] <= 0 || interval_ends[k] < interval_starts[k] || (k > 0 && interval_starts[k] <= interval_ends[k - 1])) return PISCES_E_INVALID_ARG;
+        prefix[(size_t)k + 1] = prefix[(size_t)k] + ((int64_t)interval_ends[k] - interval_starts[k] + 1);
+    }
+    const int32_t* const starts_end = interval_starts + n_intervals;
+    const int32_t* const ends_end = interval_ends + n_intervals;
+    auto count_le = [&](int64_t x) -> int64_t {   // interval positions <= x
+        const int64_t k = std::upper_bound(interval_starts, starts_end, x, [](int64_t v, int32_t s) { return v < (int64_t)s; }) - interval_starts;
+        if (k == 0) return 0;
+        return prefix[(size_t)k - 1] + (std::min<int64_t>(x, interval_ends[k - 1]) - interval_starts[k - 1] + 1);
+    };
+    auto position_of = [&](int64_t t) -> int64_t {   // the t-th interval position, 0 <= t < prefix[n_intervals]
+        const int64_t k = (std::upper_bound(prefix.begin(), prefix.end(), t) - prefix.begin()) - 1;
+        return (int64_t)interval_starts[k] + (t - prefix[(size_t)k]);
+    };
+    auto ends_below = [&](int64_t s) -> int64_t {   // intervals whose end < s
+        return std::lower_bound(interval_ends, ends_end, s, [](int32_t e, int64_t v) { return (int64_t)e < v; }) - interval_ends;
+    };
+    PiscesVcfPadState st = *state_in;
+    // states the closed form is not the mapper's walk for: neither zero-initialisation nor the formatter leaves them
+    if (st.last_variant_position_written < 0 || st.last_padded_position < 0 || st.last_cleared_interval_index < -1) return PISCES_E_UNSUPPORTED;
+    if (st.last_padded_position > st.last_variant_position_written && (int64_t)st.last_cleared_interval_index + 1 < (int64_t)n_intervals) return PISCES_E_UNSUPPORTED;
+    // pad rows come from the intervals behind the cleared ones only
+    const int64_t floor = (st.last_cleared_interval_index >= 0 && n_intervals > 0)
+                              ? (int64_t)interval_ends[std::min(st.last_cleared_interval_index, n_intervals - 1)] + 1 : 1;
+    int64_t W = st.last_variant_position_written, L = st.last_padded_position, pads = 0, written = 0, cleared = 0;
+    auto gap = [&](int64_t hi, bool asked) {   // pad rows of [max(W, L) + 1, hi], then the mapper's cursor
+        const int64_t lo = std::max(std::max(W, L) + 1, floor);
+        const int64_t k = lo <= hi ? count_le(hi) - count_le(lo - 1) : 0;
+        if (k > 0) {
+            pads += k;
+            W = L = position_of(count_le(hi) - 1);
+        }
+        if (asked) cleared = std::max(cleared, ends_below(W + 1));
+    };
+    for (int64_t i = 0; i < n; i++) {
+        const int64_t at = recs[i].position;
+        if (at < 1 || at < (i > 0 ? (int64_t)recs[i - 1].position : W)) return PISCES_E_UNSUPPORTED;   // the closed form needs rows in order
+        if (crush && i > 0 && recs[i - 1].position == recs[i].position) continue;
+        gap(at - 1, W == 0 || W + 1 < at);   // VcfFileWriter.PadIfNeeded asks the mapper only then
+        W = at;
+        written++;
+    }
+    if (finish) {   // WriteRemaining
+        gap(INT32_MAX, true);
+        W = 0;
+    }
+    st.last_variant_position_written = (int32_t)W;
+    st.last_padded_position = (int32_t)L;
+    st.last_cleared_interval_index = (int32_t)std::max<int64_t>(st.last_cleared_interval_index, cleared - 1);
+    if (pad_rows) *pad_rows = pads;
+    if (lines) *lines = written + pads;
+    if (state_out) *state_out = st;
+    return PISCES_OK;
     } catch (...) {
         return PISCES_E_INTERNAL;
     }

@@ -901,6 +901,23 @@ def new_pad_state():
     return _abi.PiscesVcfPadState(0, 0, -1)
 
 
+def vcf_pad_plan(records, intervals, state, finish=False, crush=False):
+    """pisces_hip_vcf_pad_plan: what format_vcf(..., pad=dict(state=state, intervals=intervals, finish=finish)) would do without
+    writing a line — (no-call rows, lines, the PiscesVcfPadState afterwards).  `state` is left as it is.  Raises PiscesHipError with
+    E_UNSUPPORTED for rows in descending order or a state the formatter does not produce (the formatter itself still takes those)."""
+    recs = np.ascontiguousarray(records, dtype=_abi.CALLED_ALLELE_DTYPE)
+    iv = np.asarray(intervals, dtype=np.int32).reshape(-1, 2)
+    starts, ends = np.ascontiguousarray(iv[:, 0]), np.ascontiguousarray(iv[:, 1])
+    pads, lines, out = C.c_int64(0), C.c_int64(0), _abi.PiscesVcfPadState()
+    rc = lib.pisces_hip_vcf_pad_plan(recs.ctypes.data if len(recs) else None, len(recs), int(bool(crush)), starts.ctypes.data if len(iv) else None,
+                                     ends.ctypes.data if len(iv) else None, len(iv), C.byref(state), int(bool(finish)), C.byref(pads), C.byref(lines),
+                                     C.byref(out))
+    if rc != 0:
+        raise PiscesHipError(int(rc), "vcf_pad_plan: intervals that are not positive, sorted and disjoint" if rc == _abi.E_INVALID_ARG else
+                             "vcf_pad_plan: rows in descending order, or a state the formatter does not produce")
+    return pads.value, lines.value, out
+
+
 def format_vcf(chrom, records, vcf_config=None, alleles=None, pad=None, posteriors=None, **overrides):
     """VCF body lines of `records` (pisces_hip_format_vcf[_padded][_ex]).  posteriors: the POSTERIORS_DTYPE array Posteriors() returned for
     these rows (the GP column of PloidyModel.DiploidByAdaptiveGT), None = none.  alleles: the (ref, alt) string pairs CallWithAlleles returned, needed
@@ -943,7 +960,14 @@ def format_vcf(chrom, records, vcf_config=None, alleles=None, pad=None, posterio
         starts = np.array([a for a, _ in pad["intervals"]], dtype=np.int32)
         ends = np.array([b for _, b in pad["intervals"]], dtype=np.int32)
         n_iv, finish, state = len(starts), int(bool(pad.get("finish"))), pad["state"]
-    cap = 256 * max(n, 1) + 128 * (int((ends - starts + 1).sum()) if pad is not None and n_iv else 0)
+    pad_rows = 0
+    if pad is not None and n_iv:   # the call's own no-call rows where the plan gives them, every interval position where it does not
+        pad_rows = int((ends.astype(np.int64) - starts + 1).sum())
+        planned, planned_lines = C.c_int64(0), C.c_int64(0)
+        if lib.pisces_hip_vcf_pad_plan(recs.ctypes.data if n else None, n, int(cfg.crush), starts.ctypes.data, ends.ctypes.data, n_iv,
+                                       C.byref(state), finish, C.byref(planned), C.byref(planned_lines), None) == 0:
+            pad_rows = planned.value
+    cap = 256 * max(n, 1) + (128 + len(chrom)) * pad_rows
     while True:
         buf = C.create_string_buffer(max(cap, 1))
         need = lib.pisces_hip_format_vcf_padded_ex(
