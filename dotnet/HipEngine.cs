@@ -1,6 +1,6 @@
 // HipEngine.cs — the managed half of the drop-in: one native handle per (BAM, chromosome) job, the read staging buffers, the option ->
 // PiscesHipConfig mapping and the record -> CalledAllele conversion.  Source only: this image has no dotnet toolchain (INTEGRATION.md).
-// It is written against the reference's types (Pisces.Domain / Pisces.Interfaces, v5.2.11) and include/pisces_hip.h (ABI 4).
+// It is written against the reference's types (Pisces.Domain / Pisces.Interfaces, v5.2.11) and include/pisces_hip.h (NativeMethods.PISCES_HIP_ABI_VERSION).
 using System;
 using System.Collections.Generic;
 using System.Runtime.InteropServices;
@@ -104,6 +104,30 @@ namespace Pisces.Hip
         {
             _exactCoverage = exact;
             NativeMethods.Check(_h, NativeMethods.pisces_hip_set_coverage_method(_h, exact ? NativeMethods.PISCES_COVERAGE_EXACT : NativeMethods.PISCES_COVERAGE_APPROXIMATE));
+        }
+
+        /// VariantCallerConfig.IndelRepeatFilter (VariantCallingParameters.IndelRepeatFilter, -RepeatFilter_ToBeRetired): above 0, the native
+        /// flush gives insertion and deletion rows FilterType.IndelRepeatLength (AlleleProcessor.cs:52-57); null or 0: off.  Any time.
+        public void SetIndelRepeatFilter(int? threshold)
+        {
+            NativeMethods.Check(_h, NativeMethods.pisces_hip_set_indel_repeat_filter(_h, threshold ?? 0));
+        }
+
+        /// What the native VCF formatters need of VcfWriterConfig (VcfFileWriter.cs:264-330): nulls become -1, IndelRepeatFilterThreshold
+        /// (the option when > 0, :303) names the R<n> filter.
+        public static PiscesVcfConfig VcfConfigFrom(Pisces.IO.VcfWriterConfig w)
+        {
+            PiscesVcfConfig c;
+            NativeMethods.Check(IntPtr.Zero, NativeMethods.pisces_hip_vcf_default_config(out c));
+            c.VariantQualityFilter = w.VariantQualityFilterThreshold ?? -1;
+            c.RMxNMaxRepeatLength = w.RMxNFilterMaxLengthRepeat ?? -1; c.RMxNMinRepetitions = w.RMxNFilterMinRepetitions ?? -1;
+            c.NoiseLevel = w.EstimatedBaseCallQuality;
+            c.OutputStrandBiasAndNoiseLevel = w.ShouldOutputStrandBiasAndNoiseLevel ? 1 : 0; c.OutputNoCallFraction = w.ShouldOutputNoCallFraction ? 1 : 0;
+            c.MinFrequencyThreshold = w.MinFrequencyThreshold; c.FrequencyFilterThreshold = w.FrequencyFilterThreshold ?? -1f;
+            c.Crush = w.AllowMultipleVcfLinesPerLoci ? 0 : 1;
+            c.NoiseLevelFromRecords = 1;
+            c.IndelRepeatFilter = w.IndelRepeatFilterThreshold ?? 0;
+            return c;
         }
 
         /// What ExactCoverageCalculator needs of IAlleleSource.GetSpanningReadSummaries(preceding, trailing): the spanning reads by direction
@@ -350,7 +374,7 @@ namespace Pisces.Hip
         // native filter bit -> FilterType, in the order AlleleProcessor / the genotyper / AlleleCaller add them
         private static readonly Tuple<int, FilterType>[] FilterOrder = {
             Tuple.Create(4, FilterType.LowDepth), Tuple.Create(3, FilterType.LowVariantQscore), Tuple.Create(12, FilterType.NoCall),
-            Tuple.Create(0, FilterType.StrandBias), Tuple.Create(9, FilterType.RMxN), Tuple.Create(5, FilterType.LowVariantFrequency),
+            Tuple.Create(0, FilterType.StrandBias), Tuple.Create(7, FilterType.IndelRepeatLength), Tuple.Create(9, FilterType.RMxN), Tuple.Create(5, FilterType.LowVariantFrequency),
             Tuple.Create(8, FilterType.MultiAllelicSite), Tuple.Create(6, FilterType.LowGenotypeQuality) };
 
         private static Genotype MapGenotype(int code)   // PISCES_GT_* (include/pisces_hip.h)

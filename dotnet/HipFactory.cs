@@ -67,6 +67,7 @@ namespace Pisces.Hip
             _engine.SetForcedAlleles(_forcedGtAlleles);   // -forcedalleles: ForcedReport rows, reference rows at forced positions
             _engine.SetAmpliconBiasFilter(_options.VariantCallingParameters.AmpliconBiasFilterThreshold);   // Factory.ShouldTrackAmpliconCounts (null: off)
             _engine.SetCoverageMethod(_options.CoverageMethod == Pisces.Domain.Types.CoverageMethod.Exact);   // Factory.CreateCoverageCalculator / trackReadSummaries (Factory.cs:130,184-185)
+            _engine.SetIndelRepeatFilter(_options.VariantCallingParameters.IndelRepeatFilter);   // VariantCallerConfig.IndelRepeatFilter (Factory.cs:149-179); null / 0: off
             return new HipStateManager(_engine);
         }
 

@@ -14,6 +14,7 @@ namespace Pisces.Hip
         public float MinFrequencyThreshold, FrequencyFilterThreshold;
         public int Crush;   // !AllowMultipleVcfLinesPerLoci
         public int NoiseLevelFromRecords;   // 1: the NL column is the record's NoiseLevelApplied (records made by this library)
+        public int IndelRepeatFilter;       // VcfWriterConfig.IndelRepeatFilterThreshold (names R<n>); <= 0 = null
     }
 
     [StructLayout(LayoutKind.Sequential)]
@@ -116,6 +117,7 @@ namespace Pisces.Hip
     {
         private const string Lib = "pisceship";   // libpisceship.so next to Pisces.dll (like libFileCompression.so)
 
+        public const int PISCES_HIP_ABI_VERSION = 9;   // include/pisces_hip.h: what pisces_hip_abi_version() must return for these declarations
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pisces_hip_abi_version();
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pisces_hip_default_config(out PiscesHipConfig cfg);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pisces_hip_create(ref PiscesHipConfig cfg, int device, out IntPtr handle);
@@ -244,6 +246,8 @@ namespace Pisces.Hip
         // CoverageMethod.Exact: the switch, the counts ExactCoverageCalculator needs of GetSpanningReadSummaries, and the per-read decision's host form
         public const int PISCES_COVERAGE_APPROXIMATE = 0, PISCES_COVERAGE_EXACT = 1;
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pisces_hip_set_coverage_method(IntPtr handle, int method);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pisces_hip_set_indel_repeat_filter(IntPtr handle, int threshold);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pisces_hip_indel_repeat_length(int category, int position, byte[] refAllele, int refLen, byte[] altAllele, int altLen, byte[] referenceBases, long refLength);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pisces_hip_get_spanning_read_counts(IntPtr handle, int preceding, int trailing, int isInsertion, [Out] int[] counts);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pisces_hip_exact_span_direction(int cs, int ce, byte[] cigarOp, uint[] cigarLen, int nCigar, byte[] dirRunType, uint[] dirRunLen, int nRuns, int preceding, int trailing, int isInsertion);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pisces_hip_vcf_default_config(out PiscesVcfConfig cfg);

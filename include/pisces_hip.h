@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define PISCES_HIP_ABI_VERSION 8
+#define PISCES_HIP_ABI_VERSION 9
 
 /* ---- error codes -------------------------------------------------------- */
 #define PISCES_OK                 0
@@ -767,6 +767,8 @@ typedef struct PiscesVcfConfig {
     int32_t noise_level_from_records;           /* 1: the NL column is the record's noise_level (CalledAllele.NoiseLevelApplied: records made by
                                                    this library, exact with NoiseModel.Window too); 0: noise_level above for every allele
                                                    with support (records assembled elsewhere) */
+    int32_t indel_repeat_filter;                /* IndelRepeatFilterThreshold (VcfFileWriter.cs:303), names the R<n> filter of PISCES_FILTER_INDEL_REPEAT_LENGTH;
+                                                   <= 0 = null: a row's bit then prints nothing (the reference's MapFilter throws, VcfFormatter.cs:163-166) */
 } PiscesVcfConfig;
 int32_t pisces_hip_vcf_default_config(PiscesVcfConfig* cfg);
 /* One VCF body line per record, or with cfg->crush one per position (VcfFileWriter.WriteListOfColocatedAlleles, VcfFileWriter.cs:206-262
@@ -931,6 +933,27 @@ int32_t pisces_hip_exact_span_direction(int32_t cs, int32_t ce, const uint8_t* c
 enum { PISCES_COVERAGE_APPROXIMATE = 0, PISCES_COVERAGE_EXACT = 1 };
 int32_t pisces_hip_set_coverage_method(PiscesHip* h, int32_t method);
 int32_t pisces_hip_get_spanning_read_counts(PiscesHip* h, int32_t preceding, int32_t trailing, int32_t is_insertion, int32_t* out);
+
+/* ---- the indel repeat-length filter (VariantCallingParameters.IndelRepeatFilter, -RepeatFilter_ToBeRetired, FILTER R<n>) ----
+ * pisces_hip_indel_repeat_length: AlleleProcessor.ComputeIndelRepeatLength (src/exe/Pisces/Logic/VariantCalling/AlleleProcessor.cs:80-213) for ONE
+ * allele, host only, no handle.  ref_bases[i] is position i + 1 of the chromosome (upper-cased as it is read, :100-103); the alleles as
+ * PiscesCandidate carries them, anchor base first.  The variant bases (an insertion's ALT[1:], a deletion's REF[1:]) are reduced to their
+ * shortest generating unit and counted in the stretch of the reference from 50 bases upstream of position - 1 to 49 behind it, with the
+ * reference's quirks: 1 when the stretch ends within unit + 1 bases of the scan's start (an allele anchored on the last or second-to-last
+ * base), at most 48 single-base repeats to the right.  0 for SNV, MNV and Reference alleles and for an empty reference.  Any position the
+ * reference accepts is accepted, 0 and L + 1 included; where its Substring throws (position < -49 or position > L + 1, insertion, deletion
+ * or SNV) PISCES_E_INVALID_ARG, as for a null array or an insertion / deletion without its anchor base.  csrc/indel_repeat.h, written for
+ * host and device: indel_repeat_kernel compiles the same source. */
+int32_t pisces_hip_indel_repeat_length(int32_t category, int32_t position, const uint8_t* ref_allele, int32_t ref_len, const uint8_t* alt_allele,
+                                       int32_t alt_len, const uint8_t* ref_bases, int64_t ref_length);
+/* pisces_hip_set_indel_repeat_filter: threshold > 0 makes every flush (pisces_hip_flush, _ex, _view, _begin / _end*) OR
+ * 1 << PISCES_FILTER_INDEL_REPEAT_LENGTH into the filter_bits of every insertion and deletion row with threshold <= repeat length
+ * (AlleleProcessor.ApplyFilters, AlleleProcessor.cs:52-57) — forced-report rows included, nothing else of a row changes, rows of other
+ * categories cannot get it (their length is 0).  One small launch behind the candidate kernel, on the device, before the rows leave it.
+ * 0 = off, the default: a handle that is off launches nothing for it.  A negative value: PISCES_E_INVALID_ARG, the state unchanged.
+ * Any time; it holds from the next flush that makes a batch (a batch waiting for a larger buffer keeps its rows).  The tuple surface
+ * (pisces_hip_call_tiles*) has no insertions or deletions and is untouched.  Give PiscesVcfConfig.indel_repeat_filter the same value. */
+int32_t pisces_hip_set_indel_repeat_filter(PiscesHip* h, int32_t threshold);
 
 #ifdef __cplusplus
 }

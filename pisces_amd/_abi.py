@@ -7,7 +7,7 @@ import ctypes as C
 
 import numpy as np
 
-ABI_VERSION = 8
+ABI_VERSION = 9
 
 # error codes
 OK = 0
@@ -130,7 +130,7 @@ class PiscesVcfConfig(C.Structure):
     _fields_ = [("variant_quality_filter", C.c_int32), ("rmxn_max_repeat_length", C.c_int32), ("rmxn_min_repetitions", C.c_int32),
                 ("noise_level", C.c_int32), ("output_strand_bias_and_noise_level", C.c_int32), ("output_no_call_fraction", C.c_int32),
                 ("min_frequency_threshold", C.c_float), ("frequency_filter_threshold", C.c_float), ("crush", C.c_int32),
-                ("noise_level_from_records", C.c_int32)]
+                ("noise_level_from_records", C.c_int32), ("indel_repeat_filter", C.c_int32)]
 
 
 class PiscesVcfPadState(C.Structure):

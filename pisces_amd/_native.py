@@ -30,6 +30,7 @@ EXPORTS = [
     "pisces_hip_intern_amplicon_name",
     "pisces_hip_exact_span_direction", "pisces_hip_set_coverage_method", "pisces_hip_get_spanning_read_counts",
     "pisces_hip_format_vcf_device",
+    "pisces_hip_indel_repeat_length", "pisces_hip_set_indel_repeat_filter",
 ]
 
 
@@ -132,6 +133,8 @@ def _load():
         "pisces_hip_intern_amplicon_name": (i32, [vp, C.c_char_p, i32]),
         "pisces_hip_exact_span_direction": (i32, [i32, i32, vp, vp, i32, vp, vp, i32, i32, i32, i32]),
         "pisces_hip_set_coverage_method": (i32, [vp, i32]),
+        "pisces_hip_indel_repeat_length": (i32, [i32, i32, vp, i32, vp, i32, vp, i64]),
+        "pisces_hip_set_indel_repeat_filter": (i32, [vp, i32]),
         "pisces_hip_get_spanning_read_counts": (i32, [vp, i32, i32, i32, P(i32)]),
         "pisces_hip_call_tiles_graph_build": (i32, [vp, P(_abi.PiscesTileBatch), i32, P(i32)]),
         "pisces_hip_call_tiles_graph_launch": (i32, [vp, i32, vp]),

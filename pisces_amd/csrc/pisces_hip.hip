@@ -37,6 +37,7 @@
 #include "store_kernels.hip.h"
 #include "amplicon_kernels.hip.h"
 #include "exact_kernels.hip.h"
+#include "indel_repeat_kernels.hip.h"
 #include "finder_kernels.hip.h"
 #include "bgzf_kernels.hip.h"
 #include "bam_kernels.hip.h"
@@ -327,6 +328,9 @@ struct PiscesHip {
     bool exact_l0_set = false;                 // d_exact_words[0] holds the length of the first read the handle saw (RegionStateManager._readLength)
     DeviceBuf<int32_t> d_exact_words;          // [0] that length, [1] the last add's "some read's clip-adjusted end makes a block", [2] a launch's error word
     DeviceBuf<int32_t> d_exact_extra, d_exact_spans, d_exact_out;
+    // pisces_hip_set_indel_repeat_filter: VariantCallingParameters.IndelRepeatFilter; above 0, indel_repeat_kernel follows every pass of
+    // call_spanning_kernel whose records reach the caller (span_device_pass)
+    int32_t indel_repeat_threshold = 0;
     DeviceBuf<PiscesTile> d_tiles_x;
     DeviceBuf<PiscesTileResult> d_tr_x;
     DeviceBuf<PiscesCalledAllele> d_rec_x;
@@ -1224,6 +1228,8 @@ int32_t pisces_hip_set_owned_range(PiscesHip* h, int32_t lo, int32_t hi)
 #include "surface_amplicon.inc.h"
 
 #include "surface_exact.inc.h"
+
+#include "surface_indel_repeat.inc.h"
 
 #include "surface_vcf.inc.h"
 

@@ -1661,6 +1661,11 @@ static int32_t span_device_pass(SpanBatch& B, const std::vector<const HostCandid
                        h->d_alleles.p, h->d_ref.p, h->ref_len, h->cfg.expect_stitched_reads, h->d_cand_records.p, h->d_cand_callable.p, h->P,
                        window ? h->d_sumq.p : (const double*)nullptr, B.d_folded, wanted, h->exact_on ? (const int32_t*)h->d_exact_out.p : (const int32_t*)nullptr);
     PISCES_HIP_CHECK(h, hipGetLastError());
+    if (h->indel_repeat_threshold > 0 && wanted != kSpanningFlagsOnly) {   // FilterType.IndelRepeatLength, AlleleProcessor.cs:52-57: into the records in place, ahead of the copy-out
+        hipLaunchKernelGGL(indel_repeat_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, h->stream, h->d_cands.p, n, h->d_alleles.p, h->d_ref.p, h->ref_len,
+                           h->d_cand_callable.p, wanted == kSpanningEveryRecord ? 1 : 0, h->indel_repeat_threshold, h->d_cand_records.p);
+        PISCES_HIP_CHECK(h, hipGetLastError());
+    }
     const size_t rec_bytes = wanted == kSpanningFlagsOnly ? 0 : B.raw.size() * sizeof(PiscesCalledAllele), need = rec_bytes + B.callable.size();
     h->pcie[1] += (int64_t)need;
     if (need > h->h_cand_dl_cap) {

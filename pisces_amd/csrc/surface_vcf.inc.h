@@ -58,6 +58,11 @@ int32_t pisces_hip_format_vcf_device(PiscesHip* h, const PiscesVcfConfig* cfg, c
         A.rname_len = (int32_t)r.size();
         std::memcpy(A.rname, r.data(), r.size());
     }
+    if (cfg->indel_repeat_filter > 0) {
+        const std::string r = "R" + std::to_string(cfg->indel_repeat_filter);
+        A.iname_len = (int32_t)r.size();
+        std::memcpy(A.iname, r.data(), r.size());
+    }
     PISCES_HIP_CHECK(h, hipSetDevice(h->device));
     hipStream_t s = stream ? (hipStream_t)stream : h->stream;
     if (s != h->stream) h->foreign_stream_used = h->foreign_stream_ever = true;

@@ -137,6 +137,7 @@ int32_t pisces_hip_vcf_default_config(PiscesVcfConfig* c)
     c->min_frequency_threshold = 0.01f;
     c->frequency_filter_threshold = 0.01f;
     c->crush = 0;
+    c->indel_repeat_filter = 0;   // IndelRepeatFilterThreshold null (VcfFileWriter.cs:303)
     return PISCES_OK;
 }
 
@@ -264,13 +265,17 @@ int64_t pisces_hip_format_vcf_padded_ex(const PiscesVcfConfig* cfg, const char* 
         uint32_t seen = 0;
         // (MultiAllelicSite is added by the diploid genotyper, GenotypeCalculatorUtilities.cs:139-145, after the processor's filters
         // and before AlleleCaller's LowGQ; ForcedReport by AlleleCaller.cs:112-116, after the processor's filters and before the genotyper;
-        // AmpliconBias sits behind StrandBias and before the repeat filters, AlleleProcessor.cs:45-63, and prints as AB, VcfFormatter.cs:155-156)
-        static const int kOrder[10] = {PISCES_FILTER_LOW_DEPTH, PISCES_FILTER_LOW_VARIANT_QSCORE, PISCES_FILTER_NO_CALL, PISCES_FILTER_STRAND_BIAS,
-                                       PISCES_FILTER_AMPLICON_BIAS, PISCES_FILTER_RMXN, PISCES_FILTER_LOW_VARIANT_FREQUENCY, PISCES_FILTER_FORCED_REPORT,
+        // AmpliconBias sits behind StrandBias and before the repeat filters, AlleleProcessor.cs:45-63, and prints as AB, VcfFormatter.cs:155-156;
+        // IndelRepeatLength between AmpliconBias and RMxN, :52-60, as R<threshold>, VcfFormatter.cs:163-166)
+        static const int kOrder[11] = {PISCES_FILTER_LOW_DEPTH, PISCES_FILTER_LOW_VARIANT_QSCORE, PISCES_FILTER_NO_CALL, PISCES_FILTER_STRAND_BIAS,
+                                       PISCES_FILTER_AMPLICON_BIAS, PISCES_FILTER_INDEL_REPEAT_LENGTH, PISCES_FILTER_RMXN, PISCES_FILTER_LOW_VARIANT_FREQUENCY, PISCES_FILTER_FORCED_REPORT,
                                        PISCES_FILTER_MULTI_ALLELIC_SITE, PISCES_FILTER_LOW_GENOTYPE_QUALITY};
         for (int64_t i = g0; i < g1; i++)
             for (int f : kOrder) {
                 if (!(recs[i].filter_bits & (1u << f)) || (seen & (1u << f))) continue;
+                // IndelRepeatFilterThreshold null: the reference's MapFilter throws (VcfFormatter.cs:163-166); here the bit prints nothing,
+                // as it did before the filter had a name
+                if (f == PISCES_FILTER_INDEL_REPEAT_LENGTH && cfg->indel_repeat_filter <= 0) continue;
                 seen |= 1u << f;
                 std::string name;
                 switch (f) {
@@ -282,6 +287,7 @@ int64_t pisces_hip_format_vcf_padded_ex(const PiscesVcfConfig* cfg, const char* 
                 case PISCES_FILTER_NO_CALL: name = "NC"; break;
                 case PISCES_FILTER_STRAND_BIAS: name = "SB"; break;
                 case PISCES_FILTER_AMPLICON_BIAS: name = "AB"; break;
+                case PISCES_FILTER_INDEL_REPEAT_LENGTH: name = "R" + std::to_string(cfg->indel_repeat_filter); break;
                 case PISCES_FILTER_RMXN:
                     if (cfg->rmxn_max_repeat_length < 0 || cfg->rmxn_min_repetitions < 0) return PISCES_E_INVALID_ARG;
                     name = "R" + std::to_string(cfg->rmxn_max_repeat_length) + "x" + std::to_string(cfg->rmxn_min_repetitions);

@@ -51,6 +51,8 @@ struct VcfArgs {
     char qname[16];           // q<N>
     char rname[32];           // R<M>x<N>
     char chrom[kMaxChrom];
+    int32_t iname_len;        // 0: IndelRepeatFilterThreshold null, the bit prints nothing
+    char iname[12];           // R<threshold>
 };
 
 __device__ inline int64_t vcf_rows(const VcfArgs& A)
@@ -364,10 +366,10 @@ __device__ inline int vcf_format_row(const VcfArgs& A, int64_t i, S& s)
         alt_p = ref_p + ref_n;
     }
     // filters: each refusal of the host's loop, in its order
-    static const int kOrder[10] = {PISCES_FILTER_LOW_DEPTH, PISCES_FILTER_LOW_VARIANT_QSCORE, PISCES_FILTER_NO_CALL, PISCES_FILTER_STRAND_BIAS,
-                                   PISCES_FILTER_AMPLICON_BIAS, PISCES_FILTER_RMXN, PISCES_FILTER_LOW_VARIANT_FREQUENCY, PISCES_FILTER_FORCED_REPORT,
+    static const int kOrder[11] = {PISCES_FILTER_LOW_DEPTH, PISCES_FILTER_LOW_VARIANT_QSCORE, PISCES_FILTER_NO_CALL, PISCES_FILTER_STRAND_BIAS,
+                                   PISCES_FILTER_AMPLICON_BIAS, PISCES_FILTER_INDEL_REPEAT_LENGTH, PISCES_FILTER_RMXN, PISCES_FILTER_LOW_VARIANT_FREQUENCY, PISCES_FILTER_FORCED_REPORT,
                                    PISCES_FILTER_MULTI_ALLELIC_SITE, PISCES_FILTER_LOW_GENOTYPE_QUALITY};
-    for (int k = 0; k < 10; k++) {
+    for (int k = 0; k < 11; k++) {
         if (!(r.filter_bits & (1u << kOrder[k]))) continue;
         if (kOrder[k] == PISCES_FILTER_LOW_VARIANT_QSCORE && A.variant_quality_filter < 0) return PISCES_E_INVALID_ARG;
         if (kOrder[k] == PISCES_FILTER_RMXN && (A.rmxn_max_repeat_length < 0 || A.rmxn_min_repetitions < 0)) return PISCES_E_INVALID_ARG;
@@ -407,8 +409,9 @@ __device__ inline int vcf_format_row(const VcfArgs& A, int64_t i, S& s)
     s.put('\t');
     {
         bool any = false;
-        for (int k = 0; k < 10; k++) {
+        for (int k = 0; k < 11; k++) {
             if (!(r.filter_bits & (1u << kOrder[k]))) continue;
+            if (kOrder[k] == PISCES_FILTER_INDEL_REPEAT_LENGTH && A.iname_len <= 0) continue;   // threshold null: no name, as the host's loop
             if (any) s.put(';');
             any = true;
             switch (kOrder[k]) {
@@ -417,6 +420,7 @@ __device__ inline int vcf_format_row(const VcfArgs& A, int64_t i, S& s)
             case PISCES_FILTER_NO_CALL: put_lit(s, "NC"); break;
             case PISCES_FILTER_STRAND_BIAS: put_lit(s, "SB"); break;
             case PISCES_FILTER_AMPLICON_BIAS: put_lit(s, "AB"); break;
+            case PISCES_FILTER_INDEL_REPEAT_LENGTH: put_str(s, A.iname, A.iname_len); break;
             case PISCES_FILTER_RMXN: put_str(s, A.rname, A.rname_len); break;
             case PISCES_FILTER_LOW_VARIANT_FREQUENCY: put_lit(s, "LowVariantFreq"); break;
             case PISCES_FILTER_FORCED_REPORT: put_lit(s, "ForcedReport"); break;

@@ -126,6 +126,12 @@ class HipVariantCaller:
 
     set_coverage_method = SetCoverageMethod
 
+    def SetIndelRepeatFilter(self, threshold):
+        """VariantCallingParameters.IndelRepeatFilter (-RepeatFilter_ToBeRetired): above 0, every flush gives the insertion and deletion rows
+        whose repeat length (indel_repeat_length) reaches it FILTER_INDEL_REPEAT_LENGTH; 0 = off, the default.  Any time; from the next flush.
+        Give format_vcf / format_vcf_device indel_repeat_filter=threshold to have the bit printed as R<threshold>."""
+        _check(self._h, lib.pisces_hip_set_indel_repeat_filter(self._h, int(threshold)))
+
     def GetSpanningReadCounts(self, preceding, trailing, is_insertion=False):
         """What ExactCoverageCalculator needs of IAlleleSource.GetSpanningReadSummaries(preceding, trailing): the reads the store holds that
         span the two positions, by direction (int32[3]).  An exact handle only."""
@@ -585,7 +591,7 @@ class HipVariantCaller:
         """pisces_hip_format_vcf_device: the VCF body lines of `n` (or min(n, *d_count)) device-resident rows, written on the device and
         returned as bytes — what format_vcf returns for the same rows, encoded.  Every d_* is a torch tensor or a raw device address;
         d_count is the word compact_records leaves, d_cand_index / d_cands / d_alleles what CallWithAlleles' candidates are in device
-        memory, d_gp the compacted posteriors (the :GP column).  vcf_config / overrides as format_vcf takes them (crush is refused).
+        memory, d_gp the compacted posteriors (the :GP column).  vcf_config / overrides as format_vcf takes them (indel_repeat_filter included; crush is refused).
         The launches go to `stream` (None = the handle's own) behind whatever made the rows; the call then waits once, for the size
         word, and repeats with a buffer of that size when `capacity` (default 128 bytes a row) was short.  line_offsets=True returns
         (text, offsets) with the rows + 1 byte offsets of the lines as a numpy int64 array."""
@@ -866,6 +872,20 @@ def amplicon_bias(support, coverage, threshold):
     return (None, None) if rc < 0 else (bool(rc), chance)
 
 
+def indel_repeat_length(category, position, ref_allele, alt_allele, reference):
+    """pisces_hip_indel_repeat_length: AlleleProcessor.ComputeIndelRepeatLength for one allele (category an _abi.CAT_* value, the alleles
+    with their anchor base, reference[i] = position i + 1).  Raises PiscesHipError(E_INVALID_ARG) where the reference's Substring throws
+    (a position decidedly outside the chromosome)."""
+    as_bytes = lambda x: x.encode() if isinstance(x, str) else bytes(x)
+    r, a = as_bytes(ref_allele), as_bytes(alt_allele)
+    ref = np.frombuffer(as_bytes(reference), dtype=np.uint8) if not isinstance(reference, np.ndarray) else np.ascontiguousarray(reference, np.uint8)
+    rc = lib.pisces_hip_indel_repeat_length(int(category), int(position), r, len(r), a, len(a), ref.ctypes.data if ref.size else None, ref.size)
+    if rc < 0:
+        raise PiscesHipError(int(rc), f"indel_repeat_length: position {int(position)} is outside what a chromosome of {ref.size} bases can answer for "
+                                      "(the reference throws ArgumentOutOfRangeException), or an allele lacks its anchor base")
+    return rc
+
+
 _CIGAR_RE = None
 
 
@@ -921,7 +941,8 @@ def vcf_pad_plan(records, intervals, state, finish=False, crush=False):
 def format_vcf(chrom, records, vcf_config=None, alleles=None, pad=None, posteriors=None, **overrides):
     """VCF body lines of `records` (pisces_hip_format_vcf[_padded][_ex]).  posteriors: the POSTERIORS_DTYPE array Posteriors() returned for
     these rows (the GP column of PloidyModel.DiploidByAdaptiveGT), None = none.  alleles: the (ref, alt) string pairs CallWithAlleles returned, needed
-    for insertion / deletion / MNV rows; vcf_config: _abi.PiscesVcfConfig or None for the defaults (+ field overrides, e.g. crush=1).
+    for insertion / deletion / MNV rows; vcf_config: _abi.PiscesVcfConfig or None for the defaults (+ field overrides, e.g. crush=1,
+    indel_repeat_filter=8 for the R8 name of FILTER_INDEL_REPEAT_LENGTH).
     pad: dict(state=new_pad_state(), reference=bytes, intervals=[(start, end), ...], finish=bool) adds RegionMapper's no-call rows for
     uncovered interval positions; the state object is advanced in place."""
     cfg = vcf_config
