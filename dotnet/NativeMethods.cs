@@ -21,6 +21,31 @@ namespace Pisces.Hip
     public struct PiscesVcfPadState { public int LastVariantPositionWritten, LastPaddedPosition, LastClearedIntervalIndex; }   // start at {0, 0, -1}
 
     [StructLayout(LayoutKind.Sequential)]
+    public struct PiscesVqrOptions   // VQROptions as far as the three VQR passes read them; pisces_hip_vqr_default_options fills the reference's defaults
+    {
+        public int DoBasicChecks, DoAmpliconPositionChecks, ExtentOfEdgeRegion, LociCount, BaseQNoise, FilterQscore, MaxQscore, Reserved;
+        public double ZFactor, AlignmentWarningThreshold;
+    }
+
+    [StructLayout(LayoutKind.Sequential)]
+    public unsafe struct PiscesVqrCounts   // one CountData: ByCategory[MutationCategory - 1] and NumPossibleVariants; the entries take two (all rows, rows at an edge)
+    {
+        public fixed long ByCategory[16];
+        public long NumPossibleVariants;
+    }
+
+    [StructLayout(LayoutKind.Sequential)]
+    public unsafe struct PiscesVqrTables   // QualityRecalibrationData: phred-scaled rates by SNV category, bit c of a mask = ContainsKey(category c)
+    {
+        public fixed int Basic[12];
+        public fixed int Edge[12];
+        public fixed int EdgeRisk[12];
+        public uint BasicMask, EdgeMask;
+        public int HasEdgeRisk, Reserved;
+        public double GeneralEdgeRiskIncrease;
+    }
+
+    [StructLayout(LayoutKind.Sequential)]
     public struct PiscesHipConfig
     {
         public int AbiVersion, MinBaseCallQuality, NoiseLevel, MaxVariantQscore, MinVariantQscore, VariantQscoreFilter,
@@ -248,6 +273,12 @@ namespace Pisces.Hip
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pisces_hip_set_coverage_method(IntPtr handle, int method);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pisces_hip_set_indel_repeat_filter(IntPtr handle, int threshold);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pisces_hip_indel_repeat_length(int category, int position, byte[] refAllele, int refLen, byte[] altAllele, int altLen, byte[] referenceBases, long refLength);
+        // VariantQualityRecalibration over the rows where they lie (INTEGRATION.md): count per chromosome, tables once on the host, apply per chromosome
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pisces_hip_vqr_default_options(out PiscesVqrOptions options);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pisces_hip_vqr_count_device(IntPtr handle, ref PiscesVqrOptions options, IntPtr dRecords, long n, IntPtr dCount, long lo, long hi, IntPtr dCounts, IntPtr dSuspect, IntPtr stream);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pisces_hip_vqr_count(ref PiscesVqrOptions options, [In] PiscesCalledAllele[] records, long n, long lo, long hi, [In, Out] PiscesVqrCounts[] counts, [Out] byte[] suspect);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pisces_hip_vqr_tables(ref PiscesVqrOptions options, [In] PiscesVqrCounts[] counts, out PiscesVqrTables tables);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pisces_hip_vqr_apply_device(IntPtr handle, ref PiscesVqrOptions options, ref PiscesVqrTables tables, IntPtr dRecords, long n, IntPtr dCount, IntPtr dSuspect, IntPtr dNChanged, IntPtr stream);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pisces_hip_get_spanning_read_counts(IntPtr handle, int preceding, int trailing, int isInsertion, [Out] int[] counts);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pisces_hip_exact_span_direction(int cs, int ce, byte[] cigarOp, uint[] cigarLen, int nCigar, byte[] dirRunType, uint[] dirRunLen, int nRuns, int preceding, int trailing, int isInsertion);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pisces_hip_vcf_default_config(out PiscesVcfConfig cfg);

@@ -955,6 +955,85 @@ int32_t pisces_hip_indel_repeat_length(int32_t category, int32_t position, const
  * (pisces_hip_call_tiles*) has no insertions or deletions and is untouched.  Give PiscesVcfConfig.indel_repeat_filter the same value. */
 int32_t pisces_hip_set_indel_repeat_filter(PiscesHip* h, int32_t threshold);
 
+/* ---- VariantQualityRecalibration (VQR, src/exe/VariantQualityRecalibration/) over called-allele rows ----
+ * The stage a Pisces user runs behind the caller on FFPE and amplicon samples, on the rows where they lie instead of on the VCF read back
+ * from disk: count the 12 SNV mutation categories over all rows (SignatureSorter.StrainVcf, SignatureSorter.cs:39-90), turn the
+ * over-represented ones into noise levels (QualityRecalibration.GetRecalibrationTables, QualityRecalibration.cs:58-129), re-score those SNVs
+ * with VariantQualityCalculator.AssignPoissonQScore (UpdateAllele, :131-155) — and, with do_amplicon_position_checks, the same for the
+ * rows next to an amplicon edge (EdgeIssueCountData.cs).  Three calls, between pisces_hip_compact_records (or a flush) and the VCF writer:
+ *   pisces_hip_vqr_count_device   once per chromosome, adding into one pair of counters
+ *   pisces_hip_vqr_tables         once, on the host, from the counters
+ *   pisces_hip_vqr_apply_device   once per chromosome
+ * A row is its record alone: total_coverage is the VCF's DP, allele_support AD[1], variant_qscore QUAL; rows are uncrushed, one allele
+ * each.  A call sees the rows of ONE chromosome: the reference's "did we switch chromosome" edge (EdgeIssueCountData.cs:95) is the
+ * buffer's end here.  Not part of the library: the .counts / .edgecounts / .edgevariants files, the VQR header lines and VQRVcfWriter's
+ * re-sorting, crushed and multi-allelic diploid lines.  csrc/vqr.h, written for host and device; the kernels are csrc/vqr_kernels.hip.h. */
+/* VQROptions (src/exe/VariantQualityRecalibration/VQROptions.cs) as far as the three passes read them */
+typedef struct PiscesVqrOptions {
+    int32_t do_basic_checks;               /* DoBasicChecks, 1 */
+    int32_t do_amplicon_position_checks;   /* DoAmpliconPositionChecks, 0 */
+    int32_t extent_of_edge_region;         /* ExtentofEdgeRegion, 4: rows looked at before and behind a row; 0..64 */
+    int32_t loci_count;                    /* LociCount, -1; above 0 it replaces both NumPossibleVariants (SignatureSorter.cs:78-82) */
+    int32_t base_q_noise;                  /* BamFilterParams.MinimumBaseCallQuality, 20: baselineQNoise */
+    int32_t filter_qscore;                 /* VariantCallingParams.MinimumVariantQScoreFilter, 30: sets PISCES_FILTER_LOW_VARIANT_QSCORE */
+    int32_t max_qscore;                    /* MaxQScore, 100 */
+    int32_t reserved;
+    double  z_factor;                      /* ZFactor, 2: threshold = mean + z * sigma */
+    double  alignment_warning_threshold;   /* AlignmentWarningThreshold, 10: the host's own warning on general_edge_risk_increase */
+} PiscesVqrOptions;
+/* One CountData (CountData.cs): by_category[MutationCategory - 1] (MutationCategory.cs:12-30: AtoC AtoG AtoT CtoA CtoG CtoT GtoA GtoC GtoT
+ * TtoA TtoC TtoG Insertion Deletion Reference Other; Reference stays 0) and NumPossibleVariants.  Every entry takes two: [0] over all
+ * rows, [1] over the rows at an edge (EdgeIssueCountData). */
+typedef struct PiscesVqrCounts {
+    int64_t by_category[16];
+    int64_t num_possible_variants;
+} PiscesVqrCounts;
+/* QualityRecalibrationData (QualityRecalibration.cs:14-21): phred-scaled rates by SNV category; bit c of a mask = the table holds
+ * category c (Dictionary.ContainsKey).  edge_risk holds all 12 when has_edge_risk; -2147483648 = int.MinValue, the C# cast of a rate
+ * that is NaN or infinite (no mutation at an edge: 0 / 0). */
+typedef struct PiscesVqrTables {
+    int32_t  basic[12], edge[12], edge_risk[12];
+    uint32_t basic_mask, edge_mask;
+    int32_t  has_edge_risk;
+    int32_t  reserved;
+    double   general_edge_risk_increase;   /* GeneralEdgeRiskIncrease (:281), may be NaN or infinite */
+} PiscesVqrTables;
+int32_t pisces_hip_vqr_default_options(PiscesVqrOptions* opts);
+/* The counting pass over device-resident rows: rows [lo, hi) of d_recs[0, min(n, *d_count)) (d_count NULL: n) are counted into
+ * d_counts[2] (device memory, ADDED to: zero it once, the calls of several chromosomes sum), by MutationCategoryUtil.GetMutationCategory
+ * (MutationCategory.cs:41-81: the alleles alone, a ForcedReport row counts like any other; every row, Reference rows included, is a
+ * possible variant).  With do_amplicon_position_checks a row at an edge also counts in d_counts[1], and d_suspect[i] (n bytes) becomes 1
+ * for a row at an edge that is not Reference, 0 for every other counted row.  A row is at an edge (DidWeDetectAnEdge,
+ * EdgeIssueCountData.cs:67-118) when it has coverage and, among the extent_of_edge_region rows before and behind it in ROW order, one is
+ * missing, has less than half its coverage, or lies further away in position than in rows (rows of one position are legal).  The
+ * neighbours are read from the whole buffer, not from [lo, hi) alone: a caller that streams a chromosome in pieces brings
+ * extent_of_edge_region halo rows on either side of a piece.  Asynchronous on `stream` (NULL: the handle's own).  The totals are integer
+ * sums: identical from run to run.  PISCES_E_INVALID_ARG, each with a message: null h / opts / d_counts (d_recs with n > 0),
+ * extent_of_edge_region outside 0..64, lo / hi outside 0 <= lo <= hi <= n, do_amplicon_position_checks without d_suspect. */
+int32_t pisces_hip_vqr_count_device(PiscesHip* h, const PiscesVqrOptions* opts, const PiscesCalledAllele* d_recs, int64_t n, const int32_t* d_count,
+                                    int64_t lo, int64_t hi, PiscesVqrCounts* d_counts, uint8_t* d_suspect, void* stream);
+/* The same over host rows recs[0, n), no handle and no device: counts[2] is added to.  The message of a refusal is
+ * pisces_hip_last_error(NULL)'s, as for every entry without a handle. */
+int32_t pisces_hip_vqr_count(const PiscesVqrOptions* opts, const PiscesCalledAllele* recs, int64_t n, int64_t lo, int64_t hi, PiscesVqrCounts* counts,
+                             uint8_t* suspect);
+/* GetPhredScaledCalibratedRates and GetPhredScaledCalibratedRatesForEdges (QualityRecalibration.cs:276-381) from counts[2]; host only.
+ * basic with do_basic_checks, edge with do_amplicon_position_checks, edge_risk with both.  A category is in a table when its count is
+ * strictly above mean + z_factor * sigma of the 12 sorted SNV counts without the two lowest and the two highest; its rate is
+ * (int)PtoQ(count / NumPossibleVariants + QtoP(base_q_noise)).  The reference's quirks are kept: the first function removes Insertion /
+ * Deletion / Other / Reference from the counts it is handed, so every total the edge-risk table reads is over the 12. */
+int32_t pisces_hip_vqr_tables(const PiscesVqrOptions* opts, const PiscesVqrCounts* counts, PiscesVqrTables* tables);
+/* The update pass over device-resident rows d_recs[0, min(n, *d_count)), in place (UpdateAllele, QualityRecalibration.cs:131-155): a row
+ * whose category (MutationCounter.GetMutationCategory, MutationCounter.cs:133-172: a ForcedReport row has none) is in `basic` gets
+ * AssignPoissonQScore(allele_support, total_coverage, rate, min(variant_qscore, max_qscore)); one whose category is in `edge` and at whose
+ * position some row is a suspect (d_suspect, from the counting pass over the same rows) then gets the edge_risk rate with depth and support
+ * subsampled to 1 / QtoP(rate).  An update writes variant_qscore, genotype_qscore (the same value) and noise_level (the rate), and sets
+ * PISCES_FILTER_LOW_VARIANT_QSCORE when the new score is below filter_qscore; no bit is ever cleared, a row with variant_qscore < 1 is left
+ * alone, and so is every byte of every other row.  *d_n_changed (optional, device memory, ADDED to): the rows rewritten.  The tables
+ * travel in the kernel arguments; with no category in a table nothing is launched.  Asynchronous on `stream`.  PISCES_E_INVALID_ARG:
+ * null h / opts / tables, an edge table with do_amplicon_position_checks but without d_suspect or without has_edge_risk. */
+int32_t pisces_hip_vqr_apply_device(PiscesHip* h, const PiscesVqrOptions* opts, const PiscesVqrTables* tables, PiscesCalledAllele* d_recs, int64_t n,
+                                    const int32_t* d_count, const uint8_t* d_suspect, int64_t* d_n_changed, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -137,6 +137,27 @@ class PiscesVcfPadState(C.Structure):
     _fields_ = [("last_variant_position_written", C.c_int32), ("last_padded_position", C.c_int32), ("last_cleared_interval_index", C.c_int32)]
 
 
+class PiscesVqrOptions(C.Structure):
+    _fields_ = [("do_basic_checks", C.c_int32), ("do_amplicon_position_checks", C.c_int32), ("extent_of_edge_region", C.c_int32),
+                ("loci_count", C.c_int32), ("base_q_noise", C.c_int32), ("filter_qscore", C.c_int32), ("max_qscore", C.c_int32),
+                ("reserved", C.c_int32), ("z_factor", C.c_double), ("alignment_warning_threshold", C.c_double)]
+
+
+class PiscesVqrCounts(C.Structure):
+    _fields_ = [("by_category", C.c_int64 * 16), ("num_possible_variants", C.c_int64)]
+
+
+class PiscesVqrTables(C.Structure):
+    _fields_ = [("basic", C.c_int32 * 12), ("edge", C.c_int32 * 12), ("edge_risk", C.c_int32 * 12), ("basic_mask", C.c_uint32),
+                ("edge_mask", C.c_uint32), ("has_edge_risk", C.c_int32), ("reserved", C.c_int32), ("general_edge_risk_increase", C.c_double)]
+
+
+# MutationCategory (src/exe/VariantQualityRecalibration/MutationCategory.cs:12-30), index = enum value - 1
+VQR_CATEGORIES = ("AtoC", "AtoG", "AtoT", "CtoA", "CtoG", "CtoT", "GtoA", "GtoC", "GtoT", "TtoA", "TtoC", "TtoG", "Insertion", "Deletion",
+                  "Reference", "Other")
+VQR_INT_MIN = -2147483648   # int.MinValue: the C# cast of a rate that is NaN or infinite
+
+
 def default_config(**overrides):
     """Reference defaults after VariantCallingParameters.Validate()
     (src/lib/Pisces.Domain/Options/VariantCallingParameters.cs:57-156)."""

@@ -31,6 +31,7 @@ EXPORTS = [
     "pisces_hip_exact_span_direction", "pisces_hip_set_coverage_method", "pisces_hip_get_spanning_read_counts",
     "pisces_hip_format_vcf_device",
     "pisces_hip_indel_repeat_length", "pisces_hip_set_indel_repeat_filter",
+    "pisces_hip_vqr_default_options", "pisces_hip_vqr_count_device", "pisces_hip_vqr_count", "pisces_hip_vqr_tables", "pisces_hip_vqr_apply_device",
 ]
 
 
@@ -168,6 +169,11 @@ def _load():
                                                   P(_abi.PiscesVcfPadState), i32, vp, i64, vp]),
         "pisces_hip_vcf_pad_plan": (i32, [vp, i64, i32, vp, vp, i32, P(_abi.PiscesVcfPadState), i32, P(i64), P(i64), P(_abi.PiscesVcfPadState)]),
         "pisces_hip_format_vcf_device": (i32, [vp, P(_abi.PiscesVcfConfig), C.c_char_p, vp, i64, vp, vp, vp, vp, vp, vp, i64, vp, vp, vp]),
+        "pisces_hip_vqr_default_options": (i32, [P(_abi.PiscesVqrOptions)]),
+        "pisces_hip_vqr_count_device": (i32, [vp, P(_abi.PiscesVqrOptions), vp, i64, vp, i64, i64, vp, vp, vp]),
+        "pisces_hip_vqr_count": (i32, [P(_abi.PiscesVqrOptions), vp, i64, i64, i64, P(_abi.PiscesVqrCounts), vp]),
+        "pisces_hip_vqr_tables": (i32, [P(_abi.PiscesVqrOptions), P(_abi.PiscesVqrCounts), P(_abi.PiscesVqrTables)]),
+        "pisces_hip_vqr_apply_device": (i32, [vp, P(_abi.PiscesVqrOptions), P(_abi.PiscesVqrTables), vp, i64, vp, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(lib, name)   # AttributeError here = a declared symbol is not exported

@@ -42,6 +42,7 @@
 #include "bgzf_kernels.hip.h"
 #include "bam_kernels.hip.h"
 #include "vcf_kernels.hip.h"
+#include "vqr_kernels.hip.h"
 #include "vcf_format.h"
 
 using namespace pisces;
@@ -1232,6 +1233,8 @@ int32_t pisces_hip_set_owned_range(PiscesHip* h, int32_t lo, int32_t hi)
 #include "surface_indel_repeat.inc.h"
 
 #include "surface_vcf.inc.h"
+
+#include "surface_vqr.inc.h"
 
 int32_t pisces_hip_synchronize(PiscesHip* h)
 {

@@ -630,6 +630,26 @@ class HipVariantCaller:
                 return out, written[written >= 0]   # the rows + 1 entries the kernels wrote: min(n, *d_count) lines, then the total
             return out
 
+    def vqr_count_device(self, d_recs, n, d_counts, options=None, d_count=None, lo=0, hi=None, d_suspect=None, stream=None):
+        """pisces_hip_vqr_count_device: VariantQualityRecalibration's counting pass over rows [lo, hi) of the device-resident rows
+        d_recs[0, min(n, *d_count)), ADDED into d_counts (a device int64 tensor of 2 * 17 words, PiscesVqrCounts[2]: zero it once, the
+        calls of several chromosomes sum).  With options.do_amplicon_position_checks d_suspect (n bytes) receives the suspect byte of
+        every counted row.  Every d_* is a torch tensor or a raw device address.  Asynchronous on `stream` (None = the handle's own)."""
+        opts = options if options is not None else vqr_options()
+        ptr = lambda t: None if t is None else (int(t.data_ptr()) if hasattr(t, "data_ptr") else int(t))
+        n = int(n)
+        _check(self._h, lib.pisces_hip_vqr_count_device(self._h, C.byref(opts), ptr(d_recs), n, ptr(d_count), int(lo), n if hi is None else int(hi),
+                                                        ptr(d_counts), ptr(d_suspect), self._stream_arg(stream)))
+
+    def vqr_apply_device(self, d_recs, n, tables, options=None, d_count=None, d_suspect=None, d_n_changed=None, stream=None):
+        """pisces_hip_vqr_apply_device: the update pass over d_recs[0, min(n, *d_count)), in place, with the tables of vqr_tables and the
+        suspect bytes the counting pass left for the same rows; *d_n_changed (a device int64, optional) is ADDED the rows rewritten.
+        Asynchronous on `stream`."""
+        opts = options if options is not None else vqr_options()
+        ptr = lambda t: None if t is None else (int(t.data_ptr()) if hasattr(t, "data_ptr") else int(t))
+        _check(self._h, lib.pisces_hip_vqr_apply_device(self._h, C.byref(opts), C.byref(tables), ptr(d_recs), int(n), ptr(d_count), ptr(d_suspect),
+                                                        ptr(d_n_changed), self._stream_arg(stream)))
+
     def accumulate_tiles(self, d_tuples, d_tiles, n_tiles, d_counts, stream=None):
         _check(self._h, lib.pisces_hip_accumulate_tiles(self._h, d_tuples, d_tiles, n_tiles, d_counts, self._stream_arg(stream)))
 
@@ -884,6 +904,47 @@ def indel_repeat_length(category, position, ref_allele, alt_allele, reference):
         raise PiscesHipError(int(rc), f"indel_repeat_length: position {int(position)} is outside what a chromosome of {ref.size} bases can answer for "
                                       "(the reference throws ArgumentOutOfRangeException), or an allele lacks its anchor base")
     return rc
+
+
+def vqr_options(**overrides):
+    """PiscesVqrOptions with VQROptions' defaults (pisces_hip_vqr_default_options), fields overridden by name."""
+    opts = _abi.PiscesVqrOptions()
+    _check(None, lib.pisces_hip_vqr_default_options(C.byref(opts)))
+    for k, v in overrides.items():
+        if not hasattr(opts, k):
+            raise AttributeError(f"PiscesVqrOptions has no field {k!r}")
+        setattr(opts, k, v)
+    return opts
+
+
+def vqr_counts_array(counts=None):
+    """PiscesVqrCounts[2] ([0] all rows, [1] rows at an edge), zeroed or filled from two (by_category[16], num_possible_variants) pairs."""
+    arr = (_abi.PiscesVqrCounts * 2)()
+    for k, (by_category, num_possible) in enumerate(counts or ()):
+        arr[k].by_category[:] = [int(x) for x in by_category]
+        arr[k].num_possible_variants = int(num_possible)
+    return arr
+
+
+def vqr_count(records, options=None, lo=0, hi=None, counts=None):
+    """pisces_hip_vqr_count: the counting pass over host rows (a CALLED_ALLELE_DTYPE array).  Returns (counts, suspect): the
+    PiscesVqrCounts[2] the rows [lo, hi) were added to (`counts`, or a zeroed pair) and the suspect bytes (None with the edge checks off)."""
+    opts = options if options is not None else vqr_options()
+    recs = np.ascontiguousarray(records, dtype=_abi.CALLED_ALLELE_DTYPE)
+    n = len(recs)
+    arr = counts if counts is not None else vqr_counts_array()
+    suspect = np.zeros(max(n, 1), dtype=np.uint8) if opts.do_amplicon_position_checks else None
+    _check(None, lib.pisces_hip_vqr_count(C.byref(opts), recs.ctypes.data if n else None, n, int(lo), n if hi is None else int(hi), arr,
+                                          None if suspect is None else suspect.ctypes.data))
+    return arr, (None if suspect is None else suspect[:n])
+
+
+def vqr_tables(counts, options=None):
+    """pisces_hip_vqr_tables: the recalibration tables (PiscesVqrTables) from a PiscesVqrCounts[2]; host only."""
+    opts = options if options is not None else vqr_options()
+    tables = _abi.PiscesVqrTables()
+    _check(None, lib.pisces_hip_vqr_tables(C.byref(opts), counts, C.byref(tables)))
+    return tables
 
 
 _CIGAR_RE = None
