@@ -53,6 +53,9 @@ def build_native(force=False, verbose=False, extra_flags=(), out=None):
     tmp = f"{lib}.{os.getpid()}.tmp"
     cmd = [hipcc_path(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off",
            "-fno-fast-math", "-Wall", "-Wno-unused-function", "-x", "hip",
+           # the first kernel arguments arrive in SGPRs with the wave (gfx950 preloads up to 14 dwords): call_tiles_wave_kernel's launch
+           # values are laid out for it (kernels.hip.h, TileKernelArgs); the compiler keeps a prologue of loads for firmware without it
+           "-mllvm", "-amdgpu-kernarg-preload-count=16",
            *extra_flags, *[os.path.join(CSRC, s) for s in SOURCES], "-lpthread", "-ldl", "-o", tmp]
     if verbose:
         print(" ".join(cmd))

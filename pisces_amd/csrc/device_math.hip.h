@@ -58,6 +58,32 @@ struct DeviceParams {
     int32_t folded_first, folded_n;
 };
 
+// The fields of DeviceParams that change after pisces_hip_create and that a launch of call_tiles_wave_kernel can see changed — per flush
+// (the dirty-locus bitmap, refs_only) or per launch (variants_only, totals).  The kernel takes these by value, behind its eight launch
+// values, and reads every other field from the handle's device copy of DeviceParams, which is written once when the handle is created
+// and never again.  (The folded-count window, the other per-flush part of DeviceParams, is only ever set around a launch of
+// call_store_tiles_kernel: this kernel is never asked for it, and tile_launch_params() says so.)
+struct TileLaunchParams {
+    unsigned long long* totals;
+    const uint32_t* dirty_bits;
+    int32_t dirty_first, dirty_n;
+    int32_t refs_only, variants_only;
+};
+static_assert(sizeof(TileLaunchParams) == 32 && alignof(TileLaunchParams) == 8, "TileLaunchParams: two pointers and four dwords, no padding");
+
+__host__ __device__ inline TileLaunchParams tile_launch_params(const DeviceParams& P)
+{
+    return {P.totals, P.dirty_bits, P.dirty_first, P.dirty_n, P.refs_only, P.variants_only};
+}
+// DeviceParams as a launch sees it: the constant fields of `C`, the changing ones of `L`
+__device__ __forceinline__ void apply_launch_params(DeviceParams& C, const TileLaunchParams& L)
+{
+    C.totals = L.totals;
+    C.dirty_bits = L.dirty_bits; C.dirty_first = L.dirty_first; C.dirty_n = L.dirty_n;
+    C.folded_out = nullptr; C.folded_first = 0; C.folded_n = 0;
+    C.refs_only = L.refs_only; C.variants_only = L.variants_only;
+}
+
 __device__ __forceinline__ bool locus_is_dirty(const DeviceParams& P, int pos)
 {
     if (!P.dirty_bits) return false;

@@ -25,6 +25,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 
 #include "device_math.hip.h"
 #include "genotype_core.h"
@@ -682,6 +683,7 @@ __device__ __forceinline__ void call_phase_wave(const int* hist, const uint8_t* 
 #ifdef PISCES_TIMING
                                                 , const long long tc0, const long long tc1
 #endif
+                                                , const DeviceParams* cold_params = nullptr, const TileLaunchParams* cold_launch = nullptr
                                                 )
 {
     // ---- call phase: lane = locus; with two waves per tile wave 0 makes the Reference records and the tile directory, wave 1 the
@@ -763,8 +765,19 @@ __device__ __forceinline__ void call_phase_wave(const int* hist, const uint8_t* 
             vmask |= 1u << k;
         }
     }
-    if (__builtin_expect(__ballot(slow != 0) != 0ull, 0))
-        vmask |= slow_alleles<H>(hist, s_refwin, slow, l, pos, rt, ref_rank, ref, win_lo, win_hi, records + ((int64_t)t * kSlotsPerTile + l * 4), P);
+    if (__builtin_expect(__ballot(slow != 0) != 0ull, 0)) {
+        if (cold_params) {
+            // the cold path reads its parameters where it runs (the pointer goes through an empty asm so that these loads are its own and
+            // not the caller's, kept): what only it needs of them (err_q, ln10, ...) is then not held in registers, or spilled to VGPR
+            // lanes and read back, through the table-first pass
+            const DeviceParams* pc = cold_params;
+            asm volatile("" : "+s"(pc));
+            DeviceParams Pc = *pc;
+            apply_launch_params(Pc, *cold_launch);
+            vmask |= slow_alleles<H>(hist, s_refwin, slow, l, pos, rt, ref_rank, ref, win_lo, win_hi, records + ((int64_t)t * kSlotsPerTile + l * 4), Pc);
+        } else
+            vmask |= slow_alleles<H>(hist, s_refwin, slow, l, pos, rt, ref_rank, ref, win_lo, win_hi, records + ((int64_t)t * kSlotsPerTile + l * 4), P);
+    }
     if (NW == 2) {
         if (var_wave) s_vmask[l] = (uint8_t)vmask;
         __syncthreads();
@@ -821,30 +834,70 @@ __device__ __forceinline__ void call_phase_wave(const int* hist, const uint8_t* 
     }
 }
 
+// The argument block of call_tiles_wave_kernel as the ABI lays its parameters out.  The eight launch values are exactly the first 16 dwords:
+// what the build asks the compiler to have preloaded into SGPRs at wave start (-amdgpu-kernarg-preload-count=16 in build.py; the hardware
+// has 16 user SGPRs and two hold the block's address, so 14 dwords — up to `records` — arrive that way and the rest is loaded; on
+// firmware that does not preload, the compiler's compatibility prologue loads all of them).
+struct TileKernelArgs {
+    const uint32_t* tuples; const PiscesTile* tiles; int32_t n_tiles;
+    const uint8_t* ref; int32_t ref_start; int64_t ref_len; PiscesCalledAllele* records; PiscesTileResult* tile_results;
+    TileLaunchParams L;
+    const DeviceParams* Pd;
+};
+// (a mirror of the kernel's parameter list, which cannot itself be a struct: only scalar arguments at the head of the list are preloaded;
+// the second assertion below ties the mirror's members, in order, to the parameters of both instances)
+static_assert(offsetof(TileKernelArgs, tiles) == 8 && offsetof(TileKernelArgs, n_tiles) == 16 && offsetof(TileKernelArgs, ref) == 24 &&
+              offsetof(TileKernelArgs, ref_start) == 32 && offsetof(TileKernelArgs, ref_len) == 40 && offsetof(TileKernelArgs, records) == 48 &&
+              offsetof(TileKernelArgs, tile_results) == 56 && offsetof(TileKernelArgs, L) == 64 && offsetof(TileKernelArgs, Pd) == 96 &&
+              sizeof(TileKernelArgs) == 104, "call_tiles_wave_kernel: eight launch values in 16 dwords, TileLaunchParams, one pointer");
+
 template <int NW>
 __global__ __launch_bounds__(64 * NW, NW == 1 ? PISCES_WAVE_OCC : PISCES_WAVE2_OCC) void call_tiles_wave_kernel(
     const uint32_t* __restrict__ tuples, const PiscesTile* __restrict__ tiles, int32_t n_tiles,
     const uint8_t* __restrict__ ref, int32_t ref_start, int64_t ref_len, PiscesCalledAllele* __restrict__ records,
-    PiscesTileResult* __restrict__ tile_results, DeviceParams P, const DeviceParams* __restrict__ Pd /* the same in device memory, for the cold path */)
+    PiscesTileResult* __restrict__ tile_results, TileLaunchParams L, const DeviceParams* __restrict__ Pd /* the handle's constant parameters */)
 {
     __shared__ __attribute__((aligned(16))) int hist[2 * kWaveRegion];   // 16 KiB: [region][allele:direction row][column]
     __shared__ uint8_t s_refwin[kRefWin];
     __shared__ uint8_t s_vmask[kTile];
 
+    // The head of the launch: every wave of a single-round launch is here at the same moment, and HBM is idle until the first tuple
+    // load goes out.  So the tile descriptor is the first memory instruction (the eight launch values in front of it are the first
+    // 16 dwords of the argument block: one fetch, or none where they are preloaded into SGPRs), the n_tiles guard follows it without
+    // a wait of its own, and the histogram is cleared under the descriptor's latency.  (The grid is n_tiles workgroups; the index is
+    // clamped all the same, so that the load ahead of the guard stays inside the array whatever the grid.)
     const int t = blockIdx.x;
-    if (t >= n_tiles) return;
+    const PiscesTile tile = tiles[min(t, n_tiles - 1)];
     const int l = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    const PiscesTile tile = tiles[t];
+    {
+        int4* h4 = reinterpret_cast<int4*>(hist);
+        for (int i = threadIdx.x; i < 2 * kWaveRegion / 4; i += 64 * NW) h4[i] = make_int4(0, 0, 0, 0);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    // (behind the clearing and not in front of it: an early exit between the descriptor load and its first use would let the compiler
+    // sink the load, and the argument fetch it depends on, below the branch — the three dependent round trips this head is rid of)
+    if (t >= n_tiles) return;
 #ifdef PISCES_TIMING
     const long long tc0 = wall_clock64();
 #endif
+    // The handle's parameters are asked for with the reference window, once the first batch is on its way: their round trips (the pointer,
+    // then the block) run under that batch's.  Asked for at the very top, the wait for the pointer would also be a wait for the
+    // descriptor, in front of the clearing.  Asked for behind the stream — in front of the last batch's decode or of the barrier — the
+    // dwords the call phase reads do not fit beside what is live there: the compiler loads them in three rounds, each waited for and
+    // spilled before the next, on the tile's critical path.  Measured (profiles/tuple_head_ab.txt, the dispatches' own events): 37.6-38.1
+    // us per launch with the request in front of the barrier against 37.3-37.8 here, 0.3 us in each of three interleaved rounds;
+    // ms_per_step does not resolve the two.  What only the cold path reads of the parameters is not kept: call_phase_wave reads it
+    // again where it runs (0.4 us by the same measure).
+    uint32_t min_bq_shifted = 0;
+    DeviceParams P;
     auto setup = [&]() {
-        int4* h4 = reinterpret_cast<int4*>(hist);
-        for (int i = threadIdx.x; i < 2 * kWaveRegion / 4; i += 64 * NW) h4[i] = make_int4(0, 0, 0, 0);
+        P = *Pd;
+        apply_launch_params(P, L);
         for (int i = threadIdx.x; i < kRefWin; i += 64 * NW) {
             const int64_t ri = (int64_t)tile.start_position - kRefMargin + i - ref_start;
             s_refwin[i] = (ri >= 0 && ri < ref_len) ? ref[ri] : (uint8_t)0;
         }
+        min_bq_shifted = (uint32_t)min(max(P.min_bq, 0), 255) << 24;
         __syncthreads();
     };
 
@@ -852,7 +905,6 @@ __global__ __launch_bounds__(64 * NW, NW == 1 ? PISCES_WAVE_OCC : PISCES_WAVE2_O
         // single-round launches (NW = 2): streaming waves win the issue arbitration over waves in their call phase — the launch
         // ends with the slowest tile, and a tile that is still streaming has its whole call phase ahead of it
         if (NW == 2) __builtin_amdgcn_s_setprio(3);
-        const uint32_t min_bq_shifted = (uint32_t)min(max(P.min_bq, 0), 255) << 24;
         stream_tuples_wave<NW>(tuples, tile.tuple_begin, tile.tuple_end, l, wid, [&](uint32_t v) { accumulate_wave(hist, v, min_bq_shifted); }, setup);
     }
     __syncthreads();
@@ -865,8 +917,17 @@ __global__ __launch_bounds__(64 * NW, NW == 1 ? PISCES_WAVE_OCC : PISCES_WAVE2_O
 #ifdef PISCES_TIMING
                         , tc0, tc1
 #endif
+                        , Pd, &L
                         );
 }
+template <typename... A> struct TileKernelSignature { using type = void (*)(A...); };
+static_assert(std::is_same<decltype(&call_tiles_wave_kernel<1>), decltype(&call_tiles_wave_kernel<2>)>::value &&
+              std::is_same<decltype(&call_tiles_wave_kernel<2>),
+                           TileKernelSignature<decltype(TileKernelArgs::tuples), decltype(TileKernelArgs::tiles), decltype(TileKernelArgs::n_tiles),
+                                               decltype(TileKernelArgs::ref), decltype(TileKernelArgs::ref_start), decltype(TileKernelArgs::ref_len),
+                                               decltype(TileKernelArgs::records), decltype(TileKernelArgs::tile_results), decltype(TileKernelArgs::L),
+                                               decltype(TileKernelArgs::Pd)>::type>::value,
+              "TileKernelArgs lists call_tiles_wave_kernel's parameters in order: change the two together");
 
 // The handle's memo tables (DeviceParams), filled with the very functions the call phase would otherwise run.
 __global__ __launch_bounds__(256) void build_vq_tab_kernel(int16_t* __restrict__ tab, int32_t n_k, int32_t n_cov, DeviceParams P)

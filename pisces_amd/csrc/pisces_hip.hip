@@ -350,7 +350,10 @@ struct PiscesHip {
     DeviceBuf<double> d_sb_tab;
     DeviceBuf<double> d_sb0_tab;
     DeviceBuf<int16_t> d_gq_cap;
-    DeviceBuf<DeviceParams> d_params;   // device copy of P (what the wave kernel's out-of-line cold path reads instead of a by-value copy)
+    // Device copy of P as pisces_hip_create leaves it: where call_tiles_wave_kernel reads every field that does not change afterwards
+    // (configuration, table pointers).  The fields that do change (TileLaunchParams) travel with each launch, so this copy is never
+    // rewritten; code that makes another field of P changeable has to refresh it in stream order on h->stream.
+    DeviceBuf<DeviceParams> d_params;
     int n_cus = 256;
     void* comm = nullptr;           // ncclComm_t of the summary reduce (pisces_hip_comm_init), or nullptr
     int comm_world = 1;

@@ -195,20 +195,23 @@ static hipError_t launch_call_tiles(PiscesHip* h, hipStream_t s, const uint32_t*
         // side) and pay for it in registers (128 VGPRs for 8 tiles per CU).  Measured (tools/kbench.py, 500x): that wins up
         // to ~8 k tiles per launch (56 % vs 49 % at 2048 tiles, 62 % vs 60 % at 8192); beyond that tiles interleave on their
         // own and one wave per tile (no spills, 12 tiles per CU) streams better (68.5 % vs 66 % at 15 625 tiles).
+        // (what changes per flush or per launch travels by value; every other parameter is the handle's device copy, written at create)
+        if (h->P.folded_out) return hipErrorInvalidValue;   // (the folded counts are call_store_tiles_kernel's: TileLaunchParams does not carry them)
+        const TileLaunchParams L = tile_launch_params(h->P);
         const bool two = h->kernel_variant == 3 || (h->kernel_variant == 4 && (int64_t)n_tiles <= (int64_t)h->n_cus * 32);
         // (without events the plain launch: it is what a stream capture records as a kernel node)
         if (!two && !e0 && !e1)
             hipLaunchKernelGGL(call_tiles_wave_kernel<1>, dim3((unsigned)n_tiles), dim3(64), 0, s, d_tuples, d_tiles, n_tiles, d_ref, ref_start, ref_len,
-                               d_records, d_tr, h->P, (const DeviceParams*)h->d_params.p);
+                               d_records, d_tr, L, (const DeviceParams*)h->d_params.p);
         else if (!two)
             hipExtLaunchKernelGGL(call_tiles_wave_kernel<1>, dim3((unsigned)n_tiles), dim3(64), 0, s, e0, e1, 0u, d_tuples, d_tiles,
-                                  n_tiles, d_ref, ref_start, ref_len, d_records, d_tr, h->P, (const DeviceParams*)h->d_params.p);
+                                  n_tiles, d_ref, ref_start, ref_len, d_records, d_tr, L, (const DeviceParams*)h->d_params.p);
         else if (!e0 && !e1)
             hipLaunchKernelGGL(call_tiles_wave_kernel<2>, dim3((unsigned)n_tiles), dim3(128), 0, s, d_tuples, d_tiles, n_tiles, d_ref, ref_start, ref_len,
-                               d_records, d_tr, h->P, (const DeviceParams*)h->d_params.p);
+                               d_records, d_tr, L, (const DeviceParams*)h->d_params.p);
         else
             hipExtLaunchKernelGGL(call_tiles_wave_kernel<2>, dim3((unsigned)n_tiles), dim3(128), 0, s, e0, e1, 0u, d_tuples, d_tiles,
-                                  n_tiles, d_ref, ref_start, ref_len, d_records, d_tr, h->P, (const DeviceParams*)h->d_params.p);
+                                  n_tiles, d_ref, ref_start, ref_len, d_records, d_tr, L, (const DeviceParams*)h->d_params.p);
         return hipSuccess;
     }
     hipExtLaunchKernelGGL(call_tiles_kernel, dim3((unsigned)n_tiles), dim3(kBlock), 0, s, e0, e1, 0u, d_tuples, d_tiles, n_tiles, d_ref,
