@@ -552,11 +552,27 @@ __global__ __launch_bounds__(kBlock, 4) void call_tiles_kernel(
 #ifndef PISCES_WAVE2_OCC
 #define PISCES_WAVE2_OCC 4   // two waves per tile: 8 tiles per CU resident, 2048 on the chip
 #endif
-constexpr int kWaveUnroll = PISCES_WAVE_UNROLL;   // 16-byte loads per lane per batch; two batches are in flight
+constexpr int kWaveUnroll = PISCES_WAVE_UNROLL;   // rows (wave-wide 16-byte loads) per batch; a wave keeps two batches' worth in flight
 
-// One wave streams tuples[begin, end) through op(): two register batches of kWaveUnroll dwordx4 loads per lane in
-// ping-pong, so that the loads of the next batch are in flight while the current one is decoded (a lone wave has no
-// neighbour to hide its decode time behind).
+// One wave streams tuples[begin, end) through op() from a ring of 2 * kWaveUnroll register quads per lane.  A row is 64
+// consecutive dwordx4 of the aligned body; rows are dealt in batches of kWaveUnroll (batch b belongs to wave b % NW).  Every
+// step waits for ONE row with a counted wait (s_waitcnt vmcnt(ring - 1)), decodes its four tuples per lane and re-issues
+// that quad's load at once for the row one revolution ahead, so a wave has a full ring of loads outstanding from its first
+// load to its drain: with two whole batches that were refilled only once decoded, half of the ring held nothing in flight
+// while the other half was decoded (a lone wave has no neighbour to hide its decode time behind).
+//
+// The counted waits need every slot to hold a fixed place in the order of the loads, at the drain too, and no load may go
+// out for a row the wave does not own.  So what is irregular about a wave's rows sits at the FRONT of its sequence:
+//   * the wave's steps are numbered k' = 0 .. 16 G - 1 (G revolutions), step k' uses slot k' % 16; the first `pad` steps
+//     are empty (no load, no decode), so that the last row always sits in the last slot of the last revolution;
+//   * the segment's last batch, when it is not whole (`part` rows), is the FIRST batch its owner takes, and takes the
+//     last `part` slots of its half of the ring; the whole batches follow in ascending order, one per half revolution.
+// Revolution 0 therefore loads and decodes under a wave-uniform `k' >= pad` (the head's waits are whatever the compiler
+// makes of that: all head loads are one latency), every later revolution is straight-line code: revolutions 1 .. G - 2
+// decode and refill in one loop unrolled over the ring with its trip count known up front (no register copy between
+// slots, no mid-loop exit), the last one decodes without a refill (vmcnt(15) .. vmcnt(0)).  G == 1 (at most two batches)
+// has no refill at all.  Every index is clamped into the segment whatever the descriptor holds; lanes are masked only in
+// the segment's last row, and only when it is not whole.
 template <int NW, typename Op, typename Pre>
 __device__ __forceinline__ void stream_tuples_wave(const uint32_t* __restrict__ tuples, int64_t begin, int64_t end, int lane, int wid,
                                                    Op op, Pre pre)
@@ -568,70 +584,102 @@ __device__ __forceinline__ void stream_tuples_wave(const uint32_t* __restrict__ 
     const u32x4* __restrict__ p4 = reinterpret_cast<const u32x4*>(tuples + abegin);
     const uint32_t n4 = (uint32_t)((aend - abegin) >> 2);   // a tile's segment is < 2^32 dwordx4
     constexpr uint32_t kBatch = 64u * kWaveUnroll;
-    // wave-uniform loop control in scalar registers: a divergent-looking `break` would put the loop exit on the latch
-    // path, and the waitcnt pass would then drain the batch in flight at every loop header
-    const uint32_t nb = (uint32_t)__builtin_amdgcn_readfirstlane((int)((n4 + kBatch - 1) / kBatch));   // batches wid, wid + NW, ...
-    u32x4 cur[kWaveUnroll], nxt[kWaveUnroll];
-    // every load is unconditional (index clamped into the segment) so that the batches stay straight-line code and
-    // the waits are counted, not drained; only the last, partial batch masks its out-of-range lanes afterwards
-    auto load = [&](u32x4* v, uint32_t b) {
-#pragma unroll
-        for (int u = 0; u < kWaveUnroll; u++) {
-            const uint32_t j = min(b * kBatch + (uint32_t)u * 64u + (uint32_t)lane, n4 - 1u);
-            // streamed exactly once: non-temporal so the tuples do not evict the reference / records from L2
-            v[u] = __builtin_nontemporal_load(&p4[j]);
-        }
+    constexpr int kRing = 2 * kWaveUnroll;
+    // wave-uniform loop control in scalar registers (all of it known before the first load)
+    auto uniform = [](uint32_t x) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)x); };
+    const uint32_t rows = uniform((n4 + 63u) / 64u);
+    const uint32_t nb = uniform((n4 + kBatch - 1) / kBatch);          // batches wid, wid + NW, ... are this wave's
+    const uint32_t w = uniform((uint32_t)wid);
+    const uint32_t m = w < nb ? (nb - w + NW - 1) / NW : 0u;          // this wave's batches = its half revolutions
+    const uint32_t part = rows % kWaveUnroll;                         // rows of the last batch when it is not whole
+    const bool own = part != 0u && m != 0u && (nb - 1u) % NW == w;    // this wave takes that batch, first
+    const uint32_t mf = m - (own ? 1u : 0u);                          // its whole batches
+    const uint32_t G = (m + 1u) / 2u;                                 // revolutions
+    const uint32_t K = mf * kWaveUnroll + (own ? part : 0u);          // its rows
+    const uint32_t pad = G ? G * kRing - K : (uint32_t)kRing;         // empty steps in front (all of revolution 0 for an idle wave)
+    // first dwordx4 of (revolution g, slot 0) when that half revolution is a whole batch; modulo 2^32 in front of the wave's first
+    // whole batch, where nothing uses it
+    const uint32_t e0 = (w + NW * (mf - 2u * G)) * kBatch;
+    constexpr uint32_t kRev = 2u * NW * kBatch;                       // a slot's next row is this much further on
+    auto slot_off = [](int s) { return (uint32_t)(s / kWaveUnroll) * NW * kBatch + (uint32_t)(s % kWaveUnroll) * 64u; };
+    // revolution 0: a half that holds the short batch has it in its last `part` slots
+    const uint32_t e_part = (nb - 1u) * kBatch - (kWaveUnroll - part) * 64u;
+    const uint32_t hv_part = own ? 2u * G - m : 2u;
+    const uint32_t head0 = hv_part == 0u ? e_part : e0;
+    const uint32_t head1 = hv_part == 1u ? e_part : e0 + NW * kBatch;
+    auto head_row = [&](int s) { return (s < kWaveUnroll ? head0 : head1) + (uint32_t)(s % kWaveUnroll) * 64u; };
+    const uint32_t last_row = (n4 % 64u) ? (rows - 1u) * 64u : ~0u;   // first dwordx4 of the row that needs its lanes masked, if any
+    u32x4 q[kRing];   // no initial value: a slot is read only behind the condition it was loaded under
+    // every load's index is clamped into the segment; streamed exactly once: non-temporal so the tuples do not evict the
+    // reference / records from L2
+    auto fetch = [&](int s, uint32_t e) {
+        const uint32_t j = min(e + (uint32_t)lane, n4 - 1u);
+        q[s] = __builtin_nontemporal_load(&p4[j]);
     };
-    auto consume = [&](const u32x4* v) {
-#pragma unroll
-        for (int u = 0; u < kWaveUnroll; u++) { op(v[u].x); op(v[u].y); op(v[u].z); op(v[u].w); }
+    auto decode = [&](int s, uint32_t e, bool may_be_last) {
+        u32x4 v = q[s];
+        if (may_be_last && e == last_row && (uint32_t)lane >= n4 % 64u) v = (u32x4){~0u, ~0u, ~0u, ~0u};
+        op(v.x); op(v.y); op(v.z); op(v.w);
     };
-    // the first batch is requested before pre() (the workgroup's LDS set-up and its barrier): it is in flight while the histogram
+    // revolution 0's loads: those of steps pad .. 15 that lie in [lo, hi)
+    auto head = [&](int lo, int hi) {
+#pragma unroll
+        for (int s = lo; s < hi; s++)
+            if ((uint32_t)s >= pad) fetch(s, head_row(s));
+    };
+    // revolution 0 is requested before pre() (the workgroup's LDS set-up and its barrier): it is in flight while the histogram
     // is cleared and the reference window arrives, instead of one memory latency after them
-    // (single-round launches, NW = 2: 51.5 -> 50.4 us at config 2; the one-wave form of multi-round launches shows no difference
-    // beyond run-to-run noise and keeps the set-up first)
-    const bool streams = (uint32_t)wid < nb;
+    // (single-round launches, NW = 2: 51.5 -> 50.4 us at config 2 with one batch in front; the one-wave form of multi-round launches
+    // shows no difference beyond run-to-run noise and keeps the set-up first).  All of it, not its second half alone: at config 2
+    // the two are the same loads (pad is 8 and 10 there), and with pad < 8 a first half requested behind pre() is what revolution
+    // 0's first wait would sit on, alone in flight (the compiler drains before the first refill there: it computes addresses in
+    // the slot's own registers and cannot tell whether the head loaded into them).
     if (NW == 2) {
-        if (streams) load(cur, (uint32_t)__builtin_amdgcn_readfirstlane(wid));
+        head(0, kRing);
         __builtin_amdgcn_sched_barrier(0);
         pre();
     } else {
         pre();
-        if (streams) load(cur, (uint32_t)__builtin_amdgcn_readfirstlane(wid));
+        head(0, kRing);
     }
     for (int64_t i = begin + tid; i < abegin; i += 64 * NW) op(tuples[i]);
-    if (streams) {
-        uint32_t b = (uint32_t)__builtin_amdgcn_readfirstlane(wid);
-        const uint32_t m = (nb - b + NW - 1) / NW;   // this wave's batches
-        // explicit ping-pong over pairs of batches with a trip count known up front: no register copy between the
-        // halves (it would wait for the batch in flight) and no mid-loop exit (its latch path would make the waitcnt
-        // pass drain the batch in flight at every loop header)
-        for (uint32_t p = (m - 1) / 2; p > 0; p--) {
-            load(nxt, b + NW);
-            __builtin_amdgcn_sched_barrier(0);   // keep the next batch's loads ahead of this batch's decode
-            consume(cur);
-            __builtin_amdgcn_sched_barrier(0);
-            load(cur, b + 2 * NW);
-            __builtin_amdgcn_sched_barrier(0);
-            consume(nxt);
-            __builtin_amdgcn_sched_barrier(0);
-            b += 2 * NW;
-        }
-        if (((m - 1) & 1u) != 0) {
-            load(nxt, b + NW);
-            __builtin_amdgcn_sched_barrier(0);
-            consume(cur);
-            __builtin_amdgcn_sched_barrier(0);
+    // Revolutions 0 .. G - 2: a row is waited for (15 younger loads outstanding), decoded, and its quad requested again for the next
+    // revolution, which is whole batches always.  One loop unrolled over the ring, trip count known up front, no register copy between
+    // slots, no exit but the latch.  `skip` is pad in revolution 0 and 0 afterwards: the branch around a decode holds no load, so the
+    // counts stay exact, and revolution 0 being an iteration of this loop is what makes the head's loads and the refills share their
+    // registers (peeled, the compiler gave them 64 VGPRs each and spilled into the revolution).
+    uint32_t skip = pad;
+    uint32_t d0 = head0, d1 = head1;   // first dwordx4 of slot 0's and slot kWaveUnroll's rows in the revolution being decoded
+    uint32_t e = e0;
+    auto step = [&](int s) {
+        if ((uint32_t)s >= skip) decode(s, (s < kWaveUnroll ? d0 : d1) + (uint32_t)(s % kWaveUnroll) * 64u, s % kWaveUnroll == kWaveUnroll - 1);
+    };
+    if (G >= 2u) {
+        for (uint32_t g = G; g > 1u; g--) {
+            e += kRev;
 #pragma unroll
-            for (int u = 0; u < kWaveUnroll; u++) cur[u] = nxt[u];
-            b += NW;
+            for (int s = 0; s < kRing; s++) {
+                step(s);
+                __builtin_amdgcn_sched_barrier(0);   // a refill stays behind its slot's decode and ahead of the next slot's
+                fetch(s, e + slot_off(s));
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            skip = 0u;
+            d0 = e;
+            d1 = e + NW * kBatch;
         }
-        if (b == nb - 1 && (n4 % kBatch)) {
+        // revolution G - 1: nothing left to request, every slot holds a row (vmcnt(15) .. vmcnt(0)); the segment's last row, when
+        // this wave has it in a whole batch, is the last slot's
 #pragma unroll
-            for (int u = 0; u < kWaveUnroll; u++)
-                if (b * kBatch + (uint32_t)u * 64u + (uint32_t)lane >= n4) cur[u] = (u32x4){~0u, ~0u, ~0u, ~0u};
+        for (int s = 0; s < kRing; s++) {
+            decode(s, d1 + (uint32_t)(kWaveUnroll - 1) * 64u, s == kRing - 1);
+            __builtin_amdgcn_sched_barrier(0);
         }
-        consume(cur);
+    } else {
+        // at most two batches, all of them the head's (code of its own: shared with the revolution above, the head's conditional
+        // loads would make that one's waits drain the ring); an idle wave skips all of it
+#pragma unroll
+        for (int s = 0; s < kRing; s++) step(s);
     }
     for (int64_t i = aend + tid; i < end; i += 64 * NW) op(tuples[i]);
 }

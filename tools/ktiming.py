@@ -35,6 +35,8 @@ cuid = ((xcc * 8 + se) * 2 + sh) * 16 + cu
 u, inv, cnt = np.unique(cuid, return_inverse=True, return_counts=True)
 print(f"distinct CUs used: {len(u)}; tiles per CU min/median/max: {cnt.min()} {int(np.median(cnt))} {cnt.max()}; XCC counts {np.bincount(xcc)}")
 print("tiles/CU histogram:", dict(zip(*np.unique(cnt, return_counts=True))))
+cu_end = np.array([t1[inv == i].max() for i in range(len(u))])   # when a CU's last tile finished streaming
+print("per-CU end of streaming us  min/p10/p50/p90/p99/max:", np.round(np.percentile(cu_end, [0, 10, 50, 90, 99, 100]), 1), f"mean {cu_end.mean():.2f}")
 per = cnt[inv]
 for n in np.unique(per):
     m = per == n
