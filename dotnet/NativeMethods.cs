@@ -46,6 +46,36 @@ namespace Pisces.Hip
     }
 
     [StructLayout(LayoutKind.Sequential)]
+    public unsafe struct PiscesVennOptions   // VennVcf's VariantCallingParams and SampleAggregationParameters as far as the consensus reads them; pisces_hip_venn_default_options fills the defaults
+    {
+        public float MinFrequency, MinFrequencyFilter, PoolBiasThreshold;
+        public int MinCoverage, MaxVariantQscore, CombineQscoreMethod;
+        public fixed int Reserved[2];
+    }
+
+    [StructLayout(LayoutKind.Sequential)]
+    public struct PiscesConsensusInfo   // what AggregateAllele adds to CalledAllele: the pair's rows (-1 = absent), its case, and PoolBiasResults
+    {
+        public int RowA, RowB, ComparisonCase, AltChangedToRef;
+        public double PoolBiasScore, PoolBiasGatk;
+    }
+
+    [StructLayout(LayoutKind.Sequential)]
+    public struct PiscesVennRows   // one pool's rows as a flush gives them out
+    {
+        public IntPtr Recs;
+        public long N;
+        public IntPtr Count, CandIndex, Cands, Alleles;
+    }
+
+    [StructLayout(LayoutKind.Sequential)]
+    public struct PiscesVennOut   // the consensus, in the shape of a flush; NOut points at three longs: rows, candidates, allele bytes
+    {
+        public IntPtr Recs, CandIndex, Cands, Alleles, Info, VennA, VennB, NOut;
+        public long RowCapacity, CandCapacity, AlleleCapacity;
+    }
+
+    [StructLayout(LayoutKind.Sequential)]
     public struct PiscesHipConfig
     {
         public int AbiVersion, MinBaseCallQuality, NoiseLevel, MaxVariantQscore, MinVariantQscore, VariantQscoreFilter,
@@ -279,6 +309,14 @@ namespace Pisces.Hip
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pisces_hip_vqr_count(ref PiscesVqrOptions options, [In] PiscesCalledAllele[] records, long n, long lo, long hi, [In, Out] PiscesVqrCounts[] counts, [Out] byte[] suspect);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pisces_hip_vqr_tables(ref PiscesVqrOptions options, [In] PiscesVqrCounts[] counts, out PiscesVqrTables tables);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pisces_hip_vqr_apply_device(IntPtr handle, ref PiscesVqrOptions options, ref PiscesVqrTables tables, IntPtr dRecords, long n, IntPtr dCount, IntPtr dSuspect, IntPtr dNChanged, IntPtr stream);
+        // VennVcf's consensus of two probe pools (INTEGRATION.md).  Where a host calls it: once per chromosome, after BOTH pools' HipAlleleCaller have
+        // delivered that chromosome (their rows lie behind pisces_hip_compact_records, or were copied to the device from pisces_hip_flush_view), on the stream
+        // the rows were made on; the consensus then goes through pisces_hip_vqr_* and pisces_hip_format_vcf_device like any pool's rows (NOut is their dCount).
+        // A host without a device calls pisces_hip_venn_consensus over the pinned arrays of two flushes instead.
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pisces_hip_venn_default_options(out PiscesVennOptions options);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pisces_hip_venn_consensus_device(IntPtr handle, ref PiscesVennOptions options, ref PiscesVennRows poolA, ref PiscesVennRows poolB, ref PiscesVennOut consensus, IntPtr stream);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pisces_hip_venn_consensus(ref PiscesVennOptions options, ref PiscesVennRows poolA, ref PiscesVennRows poolB, ref PiscesVennOut consensus);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pisces_hip_venn_combine(ref PiscesVennOptions options, IntPtr variantA, IntPtr variantB, int comparisonCase, out PiscesCalledAllele row, out PiscesConsensusInfo info, [Out] int[] vqAB);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pisces_hip_get_spanning_read_counts(IntPtr handle, int preceding, int trailing, int isInsertion, [Out] int[] counts);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pisces_hip_exact_span_direction(int cs, int ce, byte[] cigarOp, uint[] cigarLen, int nCigar, byte[] dirRunType, uint[] dirRunLen, int nRuns, int preceding, int trailing, int isInsertion);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pisces_hip_vcf_default_config(out PiscesVcfConfig cfg);

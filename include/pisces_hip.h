@@ -1034,6 +1034,74 @@ int32_t pisces_hip_vqr_tables(const PiscesVqrOptions* opts, const PiscesVqrCount
 int32_t pisces_hip_vqr_apply_device(PiscesHip* h, const PiscesVqrOptions* opts, const PiscesVqrTables* tables, PiscesCalledAllele* d_recs, int64_t n,
                                     const int32_t* d_count, const uint8_t* d_suspect, int64_t* d_n_changed, void* stream);
 
+/* ---- VennVcf (src/exe/VennVcf/): the consensus of two probe pools ------------------------------------------------------------------------
+ * The two pools' rows of ONE chromosome, each sorted by position, become one consensus call set with the probe-pool-bias filter
+ * (PISCES_FILTER_POOL_BIAS, the VCF's PB): rows of a position are paired (SelectPairs), a pair is one of four cases (GetComparisonCase) and
+ * becomes one row (ConsensusBuilder.CombineVariants); several HomozygousRef calls of a position merge into the first.  The reference's
+ * quirks are kept (csrc/venn.h).  The output has the shape of a flush, so pisces_hip_format_vcf*, pisces_hip_vqr_* and
+ * every other entry over rows take it unchanged.  Where the reference defines nothing a consensus row holds the sums (coverage_by_dir,
+ * support_by_dir, num_no_calls) or the ORs (filter_bits, the three bias bits) of its components; strand_bias_score is the larger one, copied.
+ * Not part of the library: reading VCFs, file names, header lines, chromosome order across calls, the PB / VF0..DP1 columns, crushed lines. */
+typedef struct PiscesVennOptions {
+    float   min_frequency;          /* VariantCallingParams.MinimumFrequency, 0.01f */
+    float   min_frequency_filter;   /* VariantCallingParams.MinimumFrequencyFilter, 0.01f (unset, the reference raises it to MinimumFrequency) */
+    float   pool_bias_threshold;    /* SampleAggregationParameters.ProbePoolBiasThreshold, 0.5f */
+    int32_t min_coverage;           /* VariantCallingParams.MinimumCoverage, 10 */
+    int32_t max_variant_qscore;     /* VariantCallingParams.MaximumVariantQScore, 100 */
+    int32_t combine_qscore_method;  /* HowToCombineQScore: 0 = CombinePoolsAndReCalculate, 1 = TakeMin */
+    int32_t reserved[2];
+} PiscesVennOptions;
+/* What AggregateAllele adds to CalledAllele, one per consensus row (32 bytes); row_a / row_b feed the debug columns VF0/VF1/AD0/AD1/DP0/DP1 */
+typedef struct PiscesConsensusInfo {
+    int32_t row_a, row_b;           /* the pair's rows in pool A and pool B, -1 = absent; the FIRST pair's for a merged reference */
+    int32_t comparison_case;        /* VariantComparisonCase: 0 AgreedOnReference, 1 AgreedOnAlternate, 2 OneReferenceOneAlternate, 3 CanNotCombine */
+    int32_t alt_changed_to_ref;     /* PushThroughRamificationsOfGTChange cut the alleles down to "ref ." */
+    double  pool_bias_score;        /* PoolBiasResults.BiasScore, at most 1; 0 after a reference merge (the reference makes a new BiasResults) */
+    double  pool_bias_gatk;         /* PoolBiasResults.GATKBiasScore in [-100, 0]: the PB column; the maximum over a merged reference */
+} PiscesConsensusInfo;
+/* One pool's rows as a flush gives them out; every pointer in host memory for pisces_hip_venn_consensus, device-accessible for
+ * pisces_hip_venn_consensus_device (recs 16-byte aligned there). */
+typedef struct PiscesVennRows {
+    const PiscesCalledAllele* recs;
+    int64_t n;
+    const int32_t* count;           /* optional: min(n, *count) rows are there (pisces_hip_compact_records' word) */
+    const int32_t* cand_index;      /* optional; with it, cands and alleles */
+    const PiscesCandidate* cands;
+    const uint8_t* alleles;
+} PiscesVennRows;
+typedef struct PiscesVennOut {
+    PiscesCalledAllele* recs;       /* row_capacity rows */
+    int32_t* cand_index;            /* row_capacity entries, -1 = the alleles are the base codes of info */
+    PiscesCandidate* cands;         /* cand_capacity */
+    uint8_t* alleles;               /* allele_capacity bytes; a candidate's allele_offset points into them */
+    PiscesConsensusInfo* info;      /* optional, row_capacity */
+    uint8_t* venn_a;                /* optional, one byte per row of pool A: 0 in no set, 1 "and" (AgreedOnAlternate), 2 "not" (the non-reference */
+    uint8_t* venn_b;                /*   member of a OneReferenceOneAlternate or CanNotCombine pair): the four files of WriteVarsToVennFiles */
+    int64_t* n_out;                 /* [3]: rows, candidates, allele bytes of the consensus.  On the device n_out doubles as the d_count word of the
+                                       entries that follow (they read its low 32 bits, little-endian; an error word reads as no rows) */
+    int64_t row_capacity, cand_capacity, allele_capacity;
+} PiscesVennOut;
+int32_t pisces_hip_venn_default_options(PiscesVennOptions* opts);
+/* The consensus of device-resident rows.  Asynchronous on `stream` (NULL: the handle's own) and ordered behind whatever made the rows, no
+ * host wait inside.  out->n_out (device-accessible) receives the three counts.  When one of them is above its capacity nothing else is
+ * written: repeat with larger buffers (the protocol of pisces_hip_format_vcf_device's d_text_bytes).  A pool that is not sorted by position
+ * (the reference's "Vcf needs to be ordered") leaves n_out = {PISCES_E_INVALID_ARG, the pool (0 / 1), its lowest offending row} and writes
+ * nothing else.  Every call overwrites: nothing is added to what the buffers held.  The output is in position order, a position's rows in
+ * the reference's pair order, identical from run to run (no atomics take part in the ordering).  Calls of one handle share the handle's
+ * scratch (24 bytes an input row) and must be stream-ordered with respect to each other, as pisces_hip_format_vcf_device's; a call that
+ * has to grow the scratch waits first.  PISCES_E_INVALID_ARG, each with a message: null h / opts / a / b / out / out->n_out, null recs
+ * with n > 0, null output arrays with a capacity > 0, negative sizes or capacities, a cand_index without cands or alleles, thresholds
+ * outside [0, 1], an unknown combine_qscore_method, rows that are not 16-byte aligned. */
+int32_t pisces_hip_venn_consensus_device(PiscesHip* h, const PiscesVennOptions* opts, const PiscesVennRows* a, const PiscesVennRows* b,
+                                         const PiscesVennOut* out, void* stream);
+/* The same over host arrays: no handle and no device, the function the device runs.  PISCES_E_BUFFER_TOO_SMALL with the three counts in
+ * n_out and nothing else written when a capacity is too small; PISCES_E_INVALID_ARG for an unsorted pool, n_out as above. */
+int32_t pisces_hip_venn_consensus(const PiscesVennOptions* opts, const PiscesVennRows* a, const PiscesVennRows* b, const PiscesVennOut* out);
+/* One pair (CombineVariants), host only: a or b may be NULL, `comparison_case` < 0 asks GetComparisonCase.  The alleles are the base codes of
+ * info.  vq_ab (optional, [2]): VariantA / VariantB .VariantQscore as the call leaves them (PushThroughRamificationsOfGTChange rewrites them). */
+int32_t pisces_hip_venn_combine(const PiscesVennOptions* opts, const PiscesCalledAllele* a, const PiscesCalledAllele* b, int32_t comparison_case,
+                                PiscesCalledAllele* row_out, PiscesConsensusInfo* info_out, int32_t* vq_ab);
+
 #ifdef __cplusplus
 }
 #endif

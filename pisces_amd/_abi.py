@@ -152,6 +152,34 @@ class PiscesVqrTables(C.Structure):
                 ("edge_mask", C.c_uint32), ("has_edge_risk", C.c_int32), ("reserved", C.c_int32), ("general_edge_risk_increase", C.c_double)]
 
 
+class PiscesVennOptions(C.Structure):
+    _fields_ = [("min_frequency", C.c_float), ("min_frequency_filter", C.c_float), ("pool_bias_threshold", C.c_float), ("min_coverage", C.c_int32),
+                ("max_variant_qscore", C.c_int32), ("combine_qscore_method", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
+class PiscesConsensusInfo(C.Structure):
+    _fields_ = [("row_a", C.c_int32), ("row_b", C.c_int32), ("comparison_case", C.c_int32), ("alt_changed_to_ref", C.c_int32),
+                ("pool_bias_score", C.c_double), ("pool_bias_gatk", C.c_double)]
+
+
+class PiscesVennRows(C.Structure):
+    _fields_ = [("recs", C.c_void_p), ("n", C.c_int64), ("count", C.c_void_p), ("cand_index", C.c_void_p), ("cands", C.c_void_p),
+                ("alleles", C.c_void_p)]
+
+
+class PiscesVennOut(C.Structure):
+    _fields_ = [("recs", C.c_void_p), ("cand_index", C.c_void_p), ("cands", C.c_void_p), ("alleles", C.c_void_p), ("info", C.c_void_p),
+                ("venn_a", C.c_void_p), ("venn_b", C.c_void_p), ("n_out", C.c_void_p), ("row_capacity", C.c_int64), ("cand_capacity", C.c_int64),
+                ("allele_capacity", C.c_int64)]
+
+
+# VariantComparisonCase (src/exe/VennVcf/VennVcf.cs:15-21) and the Venn classes of an input row (WriteVarsToVennFiles)
+VENN_AGREED_ON_REFERENCE, VENN_AGREED_ON_ALTERNATE, VENN_ONE_REFERENCE_ONE_ALTERNATE, VENN_CAN_NOT_COMBINE = 0, 1, 2, 3
+VENN_NONE, VENN_AND, VENN_NOT = 0, 1, 2
+CONSENSUS_INFO_DTYPE = np.dtype([("row_a", "<i4"), ("row_b", "<i4"), ("comparison_case", "<i4"), ("alt_changed_to_ref", "<i4"),
+                                 ("pool_bias_score", "<f8"), ("pool_bias_gatk", "<f8")])
+
+
 # MutationCategory (src/exe/VariantQualityRecalibration/MutationCategory.cs:12-30), index = enum value - 1
 VQR_CATEGORIES = ("AtoC", "AtoG", "AtoT", "CtoA", "CtoG", "CtoT", "GtoA", "GtoC", "GtoT", "TtoA", "TtoC", "TtoG", "Insertion", "Deletion",
                   "Reference", "Other")

@@ -32,6 +32,7 @@ EXPORTS = [
     "pisces_hip_format_vcf_device",
     "pisces_hip_indel_repeat_length", "pisces_hip_set_indel_repeat_filter",
     "pisces_hip_vqr_default_options", "pisces_hip_vqr_count_device", "pisces_hip_vqr_count", "pisces_hip_vqr_tables", "pisces_hip_vqr_apply_device",
+    "pisces_hip_venn_default_options", "pisces_hip_venn_consensus_device", "pisces_hip_venn_consensus", "pisces_hip_venn_combine",
 ]
 
 
@@ -174,6 +175,10 @@ def _load():
         "pisces_hip_vqr_count": (i32, [P(_abi.PiscesVqrOptions), vp, i64, i64, i64, P(_abi.PiscesVqrCounts), vp]),
         "pisces_hip_vqr_tables": (i32, [P(_abi.PiscesVqrOptions), P(_abi.PiscesVqrCounts), P(_abi.PiscesVqrTables)]),
         "pisces_hip_vqr_apply_device": (i32, [vp, P(_abi.PiscesVqrOptions), P(_abi.PiscesVqrTables), vp, i64, vp, vp, vp, vp]),
+        "pisces_hip_venn_default_options": (i32, [P(_abi.PiscesVennOptions)]),
+        "pisces_hip_venn_consensus_device": (i32, [vp, P(_abi.PiscesVennOptions), P(_abi.PiscesVennRows), P(_abi.PiscesVennRows), P(_abi.PiscesVennOut), vp]),
+        "pisces_hip_venn_consensus": (i32, [P(_abi.PiscesVennOptions), P(_abi.PiscesVennRows), P(_abi.PiscesVennRows), P(_abi.PiscesVennOut)]),
+        "pisces_hip_venn_combine": (i32, [P(_abi.PiscesVennOptions), vp, vp, i32, vp, P(_abi.PiscesConsensusInfo), vp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(lib, name)   # AttributeError here = a declared symbol is not exported

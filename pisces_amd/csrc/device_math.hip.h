@@ -93,7 +93,7 @@ __device__ __forceinline__ bool locus_is_dirty(const DeviceParams& P, int pos)
 
 
 // ln(r) >= ilogb(r) * ln 2 for r >= 1: a logarithm-free lower bound (one v_frexp_exp) for the early-out tests
-__device__ __forceinline__ double ln_lower_bound(double r) { return (double)ilogb(r) * 0.6931471805; }
+__host__ __device__ __forceinline__ double ln_lower_bound(double r) { return (double)ilogb(r) * 0.6931471805; }
 
 // Same value as poisson_cdf, bit for bit, with an exact early-out for the dominant case of the strand-bias
 // statistics (a well-supported allele against the noise rate): when 2x <= a the series branch is taken and
@@ -101,7 +101,7 @@ __device__ __forceinline__ double ln_lower_bound(double r) { return (double)ilog
 // < 2/a <= 2, and lgamma(a) >= (a-1/2)ln a - a + ln sqrt(2 pi) (also true of the Lanczos / Stirling forms the
 // reference uses, to 1e-9).  So if E = a ln x - x - [(a-1/2)ln a - a + 0.9189385] < -40 the series value is
 // < 2e^(-39.9) < 2^-54 and the reference's `1.0 - g` rounds to exactly 1.0.
-__device__ inline double poisson_cdf_sb(double num_occurrences, double expected)
+__host__ __device__ inline double poisson_cdf_sb(double num_occurrences, double expected)
 {
     const double a = (double)(int)(num_occurrences + 1.0), x = expected;
     if (x > 0.0 && a >= 1.0 && 2.0 * x <= a) {
@@ -120,14 +120,14 @@ __device__ __forceinline__ double q_to_p_int(int q, const DeviceParams& P)
 {
     return (P.q_to_p_lut && q >= 0 && q < P.q_to_p_n) ? P.q_to_p_lut[q] : q_to_p((double)q);
 }
-__device__ __forceinline__ double p_to_q(double p) { return (-10 * log10(p)); }          // MathOperations.cs:12
+__host__ __device__ __forceinline__ double p_to_q(double p) { return (-10 * log10(p)); }          // MathOperations.cs:12
 
 // ------------------------------------------------------------------------------------------
 // MathNet.Numerics 4.5.1 (NuGet dependency of Pisces.Calculators): GammaLn (Lanczos g=10.900511),
 // GammaLowerRegularized (Cephes igam/igamc), Poisson CDF / ln PMF — the algorithm behind
 // VariantQualityCalculator.cs:36,38,47.
 // ------------------------------------------------------------------------------------------
-__device__ inline double mathnet_gamma_ln(double z)
+__host__ __device__ inline double mathnet_gamma_ln(double z)
 {
     const double dk[11] = {2.48574089138753565546e-5,  1.05142378581721974210,    -3.45687097222016235469,
                            4.51227709466894823700,     -2.98285225323576655721,   1.05639711577126713077,
@@ -143,7 +143,7 @@ __device__ inline double mathnet_gamma_ln(double z)
     return log(s) + log_two_sqrt_e_over_pi + ((z - 0.5) * log((z - 0.5 + r) / e));
 }
 
-__device__ inline double mathnet_factorial_ln(int x)
+__host__ __device__ inline double mathnet_factorial_ln(int x)
 {
     if (x <= 1) return 0.0;
     if (x < 171) {
@@ -155,7 +155,7 @@ __device__ inline double mathnet_factorial_ln(int x)
     return mathnet_gamma_ln(x + 1.0);
 }
 
-__device__ inline double mathnet_gamma_lower_regularized(double a, double x, double* gamma_ln_a)
+__host__ __device__ inline double mathnet_gamma_lower_regularized(double a, double x, double* gamma_ln_a)
 {
     const double epsilon = 0.000000000000001;
     const double big = 4503599627370496.0;
@@ -212,7 +212,7 @@ __device__ inline double mathnet_gamma_lower_regularized(double a, double x, dou
 // ------------------------------------------------------------------------------------------
 // err = MathOperations.QtoP(noise level): P.err_q with NoiseModel.Flat, the allele's own with NoiseModel.Window
 struct QParams { int32_t max_vq; double ln10; };
-__device__ inline int32_t poisson_qscore_core(int32_t callCount, int32_t coverage, double err, const QParams P)
+__host__ __device__ inline int32_t poisson_qscore_core(int32_t callCount, int32_t coverage, double err, const QParams P)
 {
     if ((callCount <= 0) || (coverage <= 0)) return 0;
     double callCountMinusOne = callCount - 1;
@@ -305,7 +305,7 @@ struct SbStats { double var_gt_zero, false_pos, coverage, support; };
 // MathNet.Numerics 4.5.1 SpecialFunctions.BetaRegularized (continued fraction with the symmetry transformation, eps = 2^-53, at most
 // 50000 rounds) and Binomial(p, n).CumulativeDistribution(x) = BetaRegularized(n - k, k + 1, 1 - p): the Diploid strand-bias model
 // (StrandBiasCalculator.cs:150-173).  Kept out of line: only germline runs reach it.
-__device__ __noinline__ double mathnet_beta_regularized(double a, double b, double x)
+__host__ __device__ __noinline__ double mathnet_beta_regularized(double a, double b, double x)
 {
     const double bt = (x == 0.0 || x == 1.0) ? 0.0
                       : exp(mathnet_gamma_ln(a + b) - mathnet_gamma_ln(a) - mathnet_gamma_ln(b) + (a * log(x)) + (b * log(1.0 - x)));
@@ -338,7 +338,7 @@ __device__ __noinline__ double mathnet_beta_regularized(double a, double b, doub
 // kDiploidOk: the kernels of the streaming-rate path instantiate the Poisson / Extended models only; the Diploid model
 // (PopulateDiploidStats :150-173) is compiled into the counts-fed and candidate kernels, where germline configurations are routed.
 template <bool kDiploidOk = false>
-__device__ inline SbStats sb_create_stats(double support, double coverage, double noiseFreq, double minVariantFreq, int model)
+__host__ __device__ inline SbStats sb_create_stats(double support, double coverage, double noiseFreq, double minVariantFreq, int model)
 {
     // CreateStats :137-148 — minDetectableSNP = noiseFreq for every non-Diploid model;
     // ChanceFalseNeg (:213) does not enter the bias score and is not part of the record.
@@ -377,7 +377,7 @@ struct SbResult { double bias_score; int acceptable, var_both, cov_both; };
 
 // which: 0 overall (F+R+S), 1 forward (F + S/2), 2 reverse (R + S/2); the stitched halves use integer division (:36-41)
 template <bool kDiploidOk = false>
-__device__ __forceinline__ SbStats sb_stats_of(int which, const int32_t cov[3], const int32_t sup[3], const DeviceParams& P)
+__host__ __device__ __forceinline__ SbStats sb_stats_of(int which, const int32_t cov[3], const int32_t sup[3], const DeviceParams& P)
 {
     const int s = which == 0 ? sup[0] + sup[1] + sup[2] : (which == 1 ? sup[0] + sup[2] / 2 : sup[1] + sup[2] / 2);
     const int c = which == 0 ? cov[0] + cov[1] + cov[2] : (which == 1 ? cov[0] + cov[2] / 2 : cov[1] + cov[2] / 2);
@@ -385,7 +385,7 @@ __device__ __forceinline__ SbStats sb_stats_of(int which, const int32_t cov[3], 
 }
 
 // AssignBiasScore (:89-105) + the both-strands rules (:57-69) from the three statistics
-__device__ __forceinline__ SbResult sb_combine(const SbStats& overall, const SbStats& fwd, const SbStats& rev, const DeviceParams& P)
+__host__ __device__ __forceinline__ SbResult sb_combine(const SbStats& overall, const SbStats& fwd, const SbStats& rev, const DeviceParams& P)
 {
     // StitchedStats (:55-56) feed only the optional strand-bias report file, not the score.
     double forwardBias = (fwd.var_gt_zero * rev.false_pos) / overall.var_gt_zero;

@@ -43,6 +43,7 @@
 #include "bam_kernels.hip.h"
 #include "vcf_kernels.hip.h"
 #include "vqr_kernels.hip.h"
+#include "venn_kernels.hip.h"
 #include "vcf_format.h"
 
 using namespace pisces;
@@ -631,6 +632,10 @@ struct PiscesHip {
     DeviceBuf<uint32_t> d_vcf_len;
     DeviceBuf<int64_t> d_vcf_chunk;
     DeviceBuf<unsigned long long> d_vcf_ctrl;
+    // pisces_hip_venn_consensus_device: a row's three prefixes inside its workgroup, workgroup totals / offsets, {lowest unsorted row, go, totals}
+    DeviceBuf<uint32_t> d_venn_prefix;
+    DeviceBuf<int64_t> d_venn_chunk;
+    DeviceBuf<unsigned long long> d_venn_ctrl;
 };
 
 #define PISCES_HIP_CHECK(h, expr)                                                              \
@@ -1238,6 +1243,8 @@ int32_t pisces_hip_set_owned_range(PiscesHip* h, int32_t lo, int32_t hi)
 #include "surface_vcf.inc.h"
 
 #include "surface_vqr.inc.h"
+
+#include "surface_venn.inc.h"
 
 int32_t pisces_hip_synchronize(PiscesHip* h)
 {

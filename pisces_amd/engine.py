@@ -650,6 +650,14 @@ class HipVariantCaller:
         _check(self._h, lib.pisces_hip_vqr_apply_device(self._h, C.byref(opts), C.byref(tables), ptr(d_recs), int(n), ptr(d_count), ptr(d_suspect),
                                                         ptr(d_n_changed), self._stream_arg(stream)))
 
+    def venn_consensus_device(self, rows_a, rows_b, out, options=None, stream=None):
+        """pisces_hip_venn_consensus_device: VennVcf's consensus of two probe pools' device-resident rows of one chromosome (rows_a, rows_b:
+        venn_rows(...) over torch tensors or raw device addresses; out: venn_out(...), whose n_out is a device-accessible int64[3] that
+        receives rows, candidates and allele bytes — or {PISCES_E_INVALID_ARG, pool, row} for an unsorted pool; nothing else is written when
+        a count is above its capacity).  Asynchronous on `stream` (None = the handle's own)."""
+        opts = options if options is not None else venn_options()
+        _check(self._h, lib.pisces_hip_venn_consensus_device(self._h, C.byref(opts), C.byref(rows_a), C.byref(rows_b), C.byref(out), self._stream_arg(stream)))
+
     def accumulate_tiles(self, d_tuples, d_tiles, n_tiles, d_counts, stream=None):
         _check(self._h, lib.pisces_hip_accumulate_tiles(self._h, d_tuples, d_tiles, n_tiles, d_counts, self._stream_arg(stream)))
 
@@ -945,6 +953,125 @@ def vqr_tables(counts, options=None):
     tables = _abi.PiscesVqrTables()
     _check(None, lib.pisces_hip_vqr_tables(C.byref(opts), counts, C.byref(tables)))
     return tables
+
+
+def venn_options(**overrides):
+    """PiscesVennOptions with VennVcf's defaults (pisces_hip_venn_default_options), fields overridden by name."""
+    opts = _abi.PiscesVennOptions()
+    _check(None, lib.pisces_hip_venn_default_options(C.byref(opts)))
+    for k, v in overrides.items():
+        if not hasattr(opts, k):
+            raise AttributeError(f"PiscesVennOptions has no field {k!r}")
+        setattr(opts, k, v)
+    return opts
+
+
+def _address(t):
+    if t is None:
+        return None
+    if hasattr(t, "data_ptr"):
+        return int(t.data_ptr())
+    if hasattr(t, "ctypes"):
+        return int(t.ctypes.data)
+    if isinstance(t, C.Array):
+        return C.addressof(t)
+    return int(t)
+
+
+def venn_rows(recs, n, count=None, cand_index=None, cands=None, alleles=None):
+    """PiscesVennRows: one pool's rows as a flush gives them out.  Every argument is a torch tensor, a numpy array, a ctypes array or a raw
+    address; the caller keeps them alive."""
+    r = _abi.PiscesVennRows()
+    r.recs, r.n, r.count, r.cand_index, r.cands, r.alleles = _address(recs), int(n), _address(count), _address(cand_index), _address(cands), _address(alleles)
+    return r
+
+
+def venn_out(recs, cand_index, cands, alleles, n_out, row_capacity, cand_capacity, allele_capacity, info=None, venn_a=None, venn_b=None):
+    """PiscesVennOut: where the consensus goes (see venn_rows for the argument kinds)."""
+    o = _abi.PiscesVennOut()
+    o.recs, o.cand_index, o.cands, o.alleles, o.info = _address(recs), _address(cand_index), _address(cands), _address(alleles), _address(info)
+    o.venn_a, o.venn_b, o.n_out = _address(venn_a), _address(venn_b), _address(n_out)
+    o.row_capacity, o.cand_capacity, o.allele_capacity = int(row_capacity), int(cand_capacity), int(allele_capacity)
+    return o
+
+
+_BASE_OF_CODE = "AGCTN"
+
+
+def candidate_table(records, alleles):
+    """(cand_index int32[n], PiscesCandidate[], allele bytes uint8[]) from the (ref, alt) string pairs of format_vcf: a pair of single
+    bases (a Reference row's alt is ".") has no candidate and reads its alleles from the base codes of info."""
+    idx_l, cand_l, pool = [], [], bytearray()
+    for rec, (r, a) in zip(records, alleles):
+        if len(r) == 1 and len(a) == 1:
+            idx_l.append(-1)
+            continue
+        c = _abi.PiscesCandidate()
+        c.position, c.category = int(rec["position"]), (int(rec["info"]) >> 4) & 7
+        c.ref_len, c.alt_len, c.allele_offset = len(r), len(a), len(pool)
+        pool += r.encode() + a.encode()
+        idx_l.append(len(cand_l))
+        cand_l.append(c)
+    return (np.array(idx_l, dtype=np.int32), (_abi.PiscesCandidate * max(len(cand_l), 1))(*cand_l),
+            np.frombuffer(bytes(pool) + b"\0", dtype=np.uint8).copy())
+
+
+def venn_consensus(records_a, records_b, options=None, alleles_a=None, alleles_b=None, capacities=None):
+    """pisces_hip_venn_consensus: VennVcf's consensus of two probe pools over host rows (CALLED_ALLELE_DTYPE arrays of one chromosome, sorted
+    by position); alleles_a / alleles_b are format_vcf's (ref, alt) pairs for pools with insertion / deletion / MNV rows.  Returns a dict:
+    records, cand_index, cands (PiscesCandidate[]), allele_bytes, alleles (the (ref, alt) pairs of the consensus rows), info
+    (CONSENSUS_INFO_DTYPE), venn_a, venn_b (one class byte per input row), n_out (rows, candidates, allele bytes).  capacities: (rows,
+    candidates, allele bytes) to offer instead of sizes that always fit; too small raises PiscesHipError(PISCES_E_BUFFER_TOO_SMALL) whose
+    n_out attribute holds the three counts."""
+    opts = options if options is not None else venn_options()
+    pools, keep = [], []
+    for recs, alleles in ((records_a, alleles_a), (records_b, alleles_b)):
+        recs = np.ascontiguousarray(recs, dtype=_abi.CALLED_ALLELE_DTYPE)
+        table = candidate_table(recs, alleles) if alleles is not None else (None, None, None)
+        keep.append((recs, table))
+        pools.append(venn_rows(recs if len(recs) else None, len(recs), None, *table))
+    (ra, ta), (rb, tb) = keep
+    n_in = len(ra) + len(rb)
+    bytes_in = sum(len(t[2]) for t in (ta, tb) if t[2] is not None)
+    caps = capacities if capacities is not None else (n_in, n_in, bytes_in)
+    recs = np.zeros(max(caps[0], 1), dtype=_abi.CALLED_ALLELE_DTYPE)
+    cand_index = np.full(max(caps[0], 1), -1, dtype=np.int32)
+    cands = (_abi.PiscesCandidate * max(caps[1], 1))()
+    pool = np.zeros(max(caps[2], 1), dtype=np.uint8)
+    info = np.zeros(max(caps[0], 1), dtype=_abi.CONSENSUS_INFO_DTYPE)
+    venn_a, venn_b = np.zeros(max(len(ra), 1), dtype=np.uint8), np.zeros(max(len(rb), 1), dtype=np.uint8)
+    n_out = np.zeros(3, dtype=np.int64)
+    out = venn_out(recs, cand_index, cands, pool, n_out, caps[0], caps[1], caps[2], info=info, venn_a=venn_a, venn_b=venn_b)
+    rc = lib.pisces_hip_venn_consensus(C.byref(opts), C.byref(pools[0]), C.byref(pools[1]), C.byref(out))
+    if rc != 0:
+        err = PiscesHipError(rc, (lib.pisces_hip_last_error(None) or b"").decode())
+        err.n_out = [int(x) for x in n_out]
+        raise err
+    n, nc, nb = (int(x) for x in n_out)
+    pairs = []
+    for i in range(n):
+        if cand_index[i] >= 0:
+            c = cands[cand_index[i]]
+            o = c.allele_offset
+            pairs.append((bytes(pool[o: o + c.ref_len]).decode("latin-1"), bytes(pool[o + c.ref_len: o + c.ref_len + c.alt_len]).decode("latin-1")))
+        else:
+            word = int(recs["info"][i])
+            is_ref = ((word >> 4) & 7) == _abi.CAT_REFERENCE
+            pairs.append((_BASE_OF_CODE[min((word >> 7) & 7, 4)], "." if is_ref else _BASE_OF_CODE[min((word >> 10) & 7, 4)]))
+    return {"records": recs[:n], "cand_index": cand_index[:n], "cands": cands, "allele_bytes": pool[:nb], "alleles": pairs, "info": info[:n],
+            "venn_a": venn_a[:len(ra)], "venn_b": venn_b[:len(rb)], "n_out": (n, nc, nb)}
+
+
+def venn_combine(a, b, options=None, comparison_case=-1):
+    """pisces_hip_venn_combine: ConsensusBuilder.CombineVariants for one pair of rows (either may be None); comparison_case < 0 asks
+    GetComparisonCase.  Returns (row, info, (VariantA.VariantQscore, VariantB.VariantQscore) as the call leaves them)."""
+    opts = options if options is not None else venn_options()
+    rows = [None if r is None else np.ascontiguousarray(np.asarray(r, dtype=_abi.CALLED_ALLELE_DTYPE).reshape(1)) for r in (a, b)]
+    row = np.zeros(1, dtype=_abi.CALLED_ALLELE_DTYPE)
+    info = _abi.PiscesConsensusInfo()
+    vq = (C.c_int32 * 2)()
+    _check(None, lib.pisces_hip_venn_combine(C.byref(opts), _address(rows[0]), _address(rows[1]), int(comparison_case), row.ctypes.data, C.byref(info), vq))
+    return row[0], info, (int(vq[0]), int(vq[1]))
 
 
 _CIGAR_RE = None
