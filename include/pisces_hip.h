@@ -341,9 +341,11 @@ int32_t pisces_hip_stage_reads(PiscesHip* h, int32_t n_reads, int64_t n_cigar_op
  * cannot read).  What an upstream stage on the device hands over — a decoder, an aligner, the bench's generator — and the form in which
  * the reads -> records rate of the device is measured (inputs resident in HBM when the timed region starts).  The arrays must
  * be complete when the call is made (synchronise the stream that made them) and are copied: the caller may reuse them when the call
- * returns.  The checks pisces_hip_add_reads makes in a host pass over the CIGARs (Read.ValidateCigar, Read.cs:603-605; position > 0,
- * RegionStateManager.cs:363-364; the blocks a read touches, :361-383) run on the device (read_prepare_kernel); same refusals, same
- * messages, the state unchanged when a read is refused. */
+ * returns — overwrite them from any stream, or free them.  (The call waits for the launch's copying workgroups to have read the last byte
+ * of every array, not for the rest of the stream.)  The checks pisces_hip_add_reads makes in a host pass over the CIGARs
+ * (Read.ValidateCigar, Read.cs:603-605; position > 0, RegionStateManager.cs:363-364; the blocks a read touches, :361-383) run on the
+ * device, in the same launch that copies the arrays (add_fused_kernel); same refusals, same messages, the state unchanged when a read is
+ * refused. */
 int32_t pisces_hip_add_device_reads(PiscesHip* h, const PiscesReadBatch* device_batch, int64_t n_cigar_ops, int64_t n_bases);
 /* Pre-expanded observations for the block grid: positions[i] is the 1-based locus of tuples[i]
  * (the tuple's locus field is ignored). */

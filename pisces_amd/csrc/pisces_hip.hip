@@ -618,6 +618,7 @@ struct PiscesHip {
     DeviceBuf<long long> d_add_stamps;
 #endif
     int32_t fused_seq = 0;                    // add_fused_kernel launches of this handle (the word the host polls for the verdict)
+    int32_t copy_pending_seq = 0;             // nonzero: that launch is still reading the caller's device arrays (store_wait_copied before the add returns)
     int32_t compact_mode = 0;                 // PISCES_HIP_COMPACT: 0 = one launch (direct sums / look-back by size), 2 = "two" (scan + gather), 3 = "lookback" always
 
     // device scratch, grow-only

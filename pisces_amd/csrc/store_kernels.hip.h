@@ -567,7 +567,7 @@ struct PrepVerdict {
     int32_t span[3];
     int32_t n_keys;      // touched blocks (all of them, also beyond capacity)
     int32_t has_eqx;     // some read has an X or = operation
-    int32_t ready;       // the launch's sequence number, stored last (system-scope release): the host may poll it instead of waiting for the stream
+    int32_t ready;       // the launch's sequence number, stored last (relaxed, system scope, behind every wave's s_waitcnt vmcnt(0)): the host may poll it instead of waiting for the stream
 };
 static_assert(sizeof(PrepVerdict) == 48, "PrepVerdict layout");
 // (run by the read workgroup of add_fused_kernel that is counted in last.  It runs while the streaming role has the memory system full — a
@@ -672,15 +672,24 @@ struct AddFusedArgs {
     uint32_t enc_min_bq;        // <= 127
     CopyRanges16 C;             // misc role
     unsigned long long* scan_state;   // [read_blocks], zero between launches: status << 62 | pool bytes << 31 | records
-    unsigned int* done;               // [1 + kPrepReplicas], zero between launches: [1 + c] read workgroups of index class c that are through, [0] classes that are
+    unsigned int* done;               // [2][1 + kPrepReplicas], zero between launches: [0][1 + c] read workgroups of index class c that are through, [0][0] classes
+                                      // that are; [1]: the same two levels for the stream and misc workgroups of a batch that is being copied (d_bases)
     long long* totals;                // [2]: records, pool bytes of the batch
     PrepVerdict* verdict;             // pinned host memory
     int32_t* keys_out;
     int32_t capacity;
-    int32_t* bad_direction;           // pinned host memory, zero at launch: set by the stream role when a per-base direction is none of 0 / 1 / 2
+    int32_t* bad_direction;           // pinned host memory, [2].  [0], zero at launch: set by the stream role when a per-base direction is none of 0 / 1 / 2;
+                                      // [1] (kAddCopiedWord): `seq`, stored by the stream or misc workgroup that is through last — the caller's arrays have been read
     int32_t seq;                      // this launch's number (nonzero): verdict->ready
     long long* stamps;                // development (PISCES_ADD_STAMPS): [16]
 };
+constexpr int kAddCopiedWord = 1;         // AddFusedArgs::bad_direction[kAddCopiedWord]
+// every load and store of this wave acknowledged: s_waitcnt vmcnt(0).  A workgroup barrier does NOT imply it: __syncthreads() is a
+// workgroup-scope fence, which the backend makes of s_waitcnt lgkmcnt(0) at most — stores to global memory may still be on their way when the
+// barrier releases the waves.  Inline assembly with a memory clobber, not __builtin_amdgcn_s_waitcnt (which the compiler takes to touch no
+// memory): no store may be scheduled behind the wait.  The order wait -> s_barrier -> store is shown by profiles/add_fused_handoff_isa.txt,
+// which is to be made again (tools/isa.sh) whenever the toolchain or add_fused_kernel changes.
+__device__ __forceinline__ void wave_wait_vmem() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 constexpr int kScanDirectBlocks = 4096;   // read workgroups up to which the candidate-slot scan adds up the words before its own (beyond: look-back)
 constexpr unsigned long long kScanAggregate = 1ull << 62, kScanInclusive = 2ull << 62, kScanField = 0x7FFFFFFFull;
 
@@ -769,8 +778,30 @@ __global__ __launch_bounds__(256, PISCES_ADD_OCC) void add_fused_kernel(AddFused
     __shared__ int s_wf[4], s_wp[4], s_excl[2], s_last;
     if (b >= A.read_blocks) {
         add_stream_roles(A, b - A.read_blocks);
-        // (the streaming roles leave nothing the collecting workgroup reads: no fence, no count — a release fence here is a write-back of the
+        // (the streaming roles leave nothing the collecting workgroup reads: no fence — a release fence here is a write-back of the
         // XCD's whole L2, and 8 000 workgroups x 4 waves of them made the launch 1.2 ms where its bytes take 45 us)
+        // A batch that is being copied out of the caller's arrays: the add may not return before the last of them has been READ.  Every wave
+        // waits for its own loads (and stores) to be acknowledged, the workgroup counts itself in — relaxed agent-scope atomics in two levels,
+        // as the read role's `done` — and the last one through tells the host.  Nothing is published by this: the host reads none of the
+        // copies, later kernels are ordered by the stream.  (Per-base directions: the host waits for the whole launch anyway.)
+        if (A.d_bases && !A.s_dirs) {
+            wave_wait_vmem();
+            __syncthreads();
+            if (threadIdx.x == 0) {
+                unsigned int* const copied = A.done + (1 + kPrepReplicas);
+                const unsigned sb = (unsigned)(b - A.read_blocks), n_wg = (unsigned)(A.stream_blocks + A.misc_blocks);
+                const unsigned cls = sb & (kPrepReplicas - 1u);
+                const unsigned members = (n_wg - cls + kPrepReplicas - 1u) / kPrepReplicas;
+                if (__hip_atomic_fetch_add(&copied[1 + cls], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == members - 1u) {
+                    __hip_atomic_store(&copied[1 + cls], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // (as the next launch expects it: this class is through)
+                    const unsigned classes = min(n_wg, (unsigned)kPrepReplicas);
+                    if (__hip_atomic_fetch_add(&copied[0], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == classes - 1u) {
+                        __hip_atomic_store(&copied[0], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        __hip_atomic_store(&A.bad_direction[kAddCopiedWord], A.seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                    }
+                }
+            }
+        }
         return;
     }
     // ---- read role
@@ -870,10 +901,12 @@ __global__ __launch_bounds__(256, PISCES_ADD_OCC) void add_fused_kernel(AddFused
     }
     }
     // The read workgroup that is through last collects.  What it reads of the others — block map, spans, first error, totals — was written
-    // with agent-scope atomics, which are performed past the XCDs' L2s, and the barrier's s_waitcnt vmcnt(0) has every wave's atomics
-    // acknowledged before thread 0 counts the workgroup in: the count is a RELAXED atomic.  (A release there is a write-back of the XCD's
-    // whole L2 — while the stream role fills it — per read workgroup: 60 us of the launch's 127; a fence in every wave of every role: 1.2 ms.)
-    // The collector reads with agent-scope atomic loads.
+    // with agent-scope atomics, which are performed past the XCDs' L2s.  Every wave waits for its own to be acknowledged (an explicit
+    // s_waitcnt vmcnt(0): the barrier alone is a bare s_barrier and waits for no store) before the barrier behind which thread 0 counts the
+    // workgroup in: the count is a RELAXED atomic.  (A release there is a write-back of the XCD's whole L2 — while the stream role fills it —
+    // per read workgroup: 60 us of the launch's 127; a fence in every wave of every role: 1.2 ms.)  The collector reads with agent-scope
+    // atomic loads.
+    wave_wait_vmem();
     __syncthreads();
     if (threadIdx.x == 0) {
         // counted in two levels — kPrepReplicas counters by workgroup index, then one for the counters that are full — so that no word sees
@@ -900,8 +933,10 @@ __global__ __launch_bounds__(256, PISCES_ADD_OCC) void add_fused_kernel(AddFused
     }
     if (threadIdx.x <= kPrepReplicas) A.done[threadIdx.x] = 0u;
     if (threadIdx.x == 0) *A.P.first_error = ~0ull;
-    // the word the host polls, behind every thread's stores to the host's memory (verdict, keys): the barrier's workgroup-scope fence has
-    // each wave wait for its stores' acknowledgements (s_waitcnt vmcnt(0)); device-to-host writes arrive in the order they were acknowledged in
+    // the word the host polls, behind every thread's stores to the host's memory (verdict, keys): each of the four waves waits for its own
+    // stores' acknowledgements (an explicit s_waitcnt vmcnt(0) — the barrier has none), then the barrier, then thread 0's store; device-to-host
+    // writes arrive in the order they were acknowledged in
+    wave_wait_vmem();
     __syncthreads();
     PISCES_STAMP(8, true);
     if (threadIdx.x == 0) __hip_atomic_store(&A.verdict->ready, A.seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);

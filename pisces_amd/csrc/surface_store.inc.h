@@ -98,6 +98,11 @@ static int32_t store_new_segment(PiscesHip* h, std::unique_ptr<ReadSegment>* out
 
 static void store_retire(PiscesHip* h, std::unique_ptr<ReadSegment> g)
 {
+    // A position grid that was kept back may be this segment's: its ShapeArgs point into the segment's blob, descriptors and grid.  It is
+    // RUN here (not dropped: the entries do not say whose they are, and running one is a launch of nr / 256 workgroups), in front of whatever
+    // pools or frees the buffers — a flush that launched nothing over the store (every tile of its blocks clipped by the intervals) came
+    // here without store_view.  (a launch error stays with the stream: the next wait reports it)
+    (void)store_run_deferred(h);
     // (kernels that read the segment are ordered before whatever reuses its buffers: one stream)
     if (h->segment_pool.size() < 4) h->segment_pool.push_back(std::move(g));
 }
@@ -107,6 +112,8 @@ static void store_retire(PiscesHip* h, std::unique_ptr<ReadSegment> g)
 static int32_t store_commit_flush(PiscesHip* h, const std::vector<int32_t>& keys)
 {
     if (h->read_path != 1 || keys.empty()) return PISCES_OK;
+    // (grids kept back are run before a segment is emptied in place, retired or floored: see store_retire)
+    { int32_t rcd = store_run_deferred(h); if (rcd) return rcd; }
     const int64_t floor64 = (int64_t)keys.back() * h->cfg.block_size + 1;
     const int32_t floor = (int32_t)std::min<int64_t>(floor64, 0x7FFFFFFFll);
     const bool none_left = h->blocks.empty();
@@ -393,6 +400,40 @@ static int32_t store_append_arrays(PiscesHip* h, const StorePlace& pl, const Sto
 // fragments and row codes are made by the same launch (store_shape_begin filled the arguments).  One wait: the verdict, the span, the
 // totals and the touched blocks arrive in pinned memory as the launch's own stores.  found_slots / found_pool: the candidate-record slots
 // (MNV calling off), scanned by the launch itself, at d + L.off_fslots.
+constexpr int32_t kPrepKeys = 8192;   // keys of touched blocks the launch reports in pinned memory (h_prep: PrepVerdict, the keys, bad direction, copied)
+// h_prep, pinned: the PrepVerdict, kPrepKeys keys, then the words the launch's stream and misc roles write ([0] bad direction, [kAddCopiedWord] copied)
+constexpr size_t kPrepBytes = sizeof(PrepVerdict) + (size_t)kPrepKeys * sizeof(int32_t) + 16;
+static inline int32_t* prep_keys(PiscesHip* h) { return (int32_t*)(h->h_prep + sizeof(PrepVerdict)); }
+static inline int32_t* prep_stream_words(PiscesHip* h) { return prep_keys(h) + kPrepKeys; }
+static inline void cpu_relax()
+{
+#if defined(__x86_64__) || defined(__i386__)
+    __builtin_ia32_pause();
+#else
+    std::this_thread::yield();
+#endif
+}
+// The copy contract of pisces_hip_add_device_reads: "the caller may reuse the arrays when the call returns".  The verdict comes from the read
+// role; the stream and misc workgroups of the same launch may still be reading the caller's bases, qualities, flags and CIGARs then.  They
+// count themselves through and the last one stores the launch's number into pinned memory (add_fused_kernel): polled here, immediately
+// before the add returns, so that the host's bookkeeping behind the verdict still runs under the copy.  A launch that never reports falls
+// back to the stream's own wait after 0.2 s, as the verdict's poll does.
+static int32_t store_wait_copied(PiscesHip* h)
+{
+    const int32_t seq = h->copy_pending_seq;
+    h->copy_pending_seq = 0;
+    if (!seq || !h->h_prep) return PISCES_OK;
+    const volatile int32_t* const copied = prep_stream_words(h) + kAddCopiedWord;
+    const auto t0 = std::chrono::steady_clock::now();
+    for (int64_t spin = 0; *copied != seq; spin++) {
+        if ((spin & 1023) == 1023 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(200)) {
+            PISCES_HIP_CHECK(h, hipStreamSynchronize(h->stream));
+            break;
+        }
+        cpu_relax();
+    }
+    return PISCES_OK;
+}
 static int32_t store_device_checks(PiscesHip* h, uint8_t* d, const StageLayout& L, int32_t nr, size_t n_cig, size_t n_seq, bool has_dirs, bool has_deldirs,
                                    bool count_indels, int64_t* found_slots, int64_t* found_pool, std::vector<int32_t>& touched, int32_t* max_key, int32_t* min_position,
                                    const PiscesReadBatch* src = nullptr, const ShapeArgs* shape = nullptr)
@@ -420,9 +461,9 @@ static int32_t store_device_checks(PiscesHip* h, uint8_t* d, const StageLayout& 
         PISCES_HIP_CHECK(h, hipMemsetAsync(h->d_prep_map.p, 0, map_words * map_copies * sizeof(uint32_t), h->stream));
         h->prep_map_clean = true;
     }
-    // the launch's shared words — kPrepReplicas x {lowest key, highest key, lowest position, X / = seen}, the first-error word, the count of
-    // workgroups that are through, the totals — are set once: the collecting workgroup of every launch leaves them as the next one expects
-    constexpr size_t kWordsSpan = 0, kWordsError = 4 * kPrepReplicas * sizeof(int32_t), kWordsDone = kWordsError + 8, kWordsTotals = kWordsDone + 8 * ((1 + kPrepReplicas) * 4 / 8 + 1), kWordsBytes = kWordsTotals + 16;
+    // the launch's shared words — kPrepReplicas x {lowest key, highest key, lowest position, X / = seen}, the first-error word, the counts of
+    // workgroups that are through (read role; stream and misc roles), the totals — are set once: the collecting workgroup of every launch leaves them as the next one expects
+    constexpr size_t kWordsSpan = 0, kWordsError = 4 * kPrepReplicas * sizeof(int32_t), kWordsDone = kWordsError + 8, kWordsTotals = kWordsDone + 8 * (2 * (1 + kPrepReplicas) * 4 / 8 + 1), kWordsBytes = kWordsTotals + 16;
     if (!h->d_fused_words.p) {
         PISCES_HIP_CHECK(h, h->d_fused_words.reserve(kWordsBytes));
         uint8_t init[kWordsBytes];
@@ -438,12 +479,12 @@ static int32_t store_device_checks(PiscesHip* h, uint8_t* d, const StageLayout& 
         PISCES_HIP_CHECK(h, h->d_fused_scan.reserve((size_t)read_blocks + 1));
         if (h->d_fused_scan.cap != before) PISCES_HIP_CHECK(h, hipMemsetAsync(h->d_fused_scan.p, 0, h->d_fused_scan.cap * sizeof(unsigned long long), h->stream));
     }
-    constexpr int32_t kPrepKeys = 8192;
-    if (!h->h_prep) PISCES_HIP_CHECK(h, host_alloc((void**)&h->h_prep, sizeof(PrepVerdict) + (size_t)kPrepKeys * sizeof(int32_t) + 16));
+    if (!h->h_prep) PISCES_HIP_CHECK(h, host_alloc((void**)&h->h_prep, kPrepBytes));
     PrepVerdict* const verdict = (PrepVerdict*)h->h_prep;
-    int32_t* const keys = (int32_t*)(h->h_prep + sizeof(PrepVerdict));
-    int32_t* const bad_direction = keys + kPrepKeys;   // (set by the launch's stream role, which no other workgroup waits for)
+    int32_t* const keys = prep_keys(h);
+    int32_t* const bad_direction = prep_stream_words(h);   // (set by the launch's stream role, which no other workgroup waits for)
     *bad_direction = 0;
+    bad_direction[kAddCopiedWord] = 0;                 // (the launch's number once the caller's arrays have been read: store_wait_copied)
     AddFusedArgs F;
     std::memset(&F, 0, sizeof(F));
     PrepareArgs& A = F.P;
@@ -518,6 +559,8 @@ static int32_t store_device_checks(PiscesHip* h, uint8_t* d, const StageLayout& 
     if (h->chain_timing && src) { PISCES_HIP_CHECK(h, hipEventRecord(h->ev_chain[0], h->stream)); h->chain_add_open = true; }
     hipLaunchKernelGGL(add_fused_kernel, dim3((unsigned)(F.read_blocks + F.stream_blocks + F.misc_blocks)), dim3(256), 0, h->stream, F);
     PISCES_HIP_CHECK(h, hipGetLastError());
+    // (the caller's arrays are read by the stream and misc roles, which the verdict does not wait for: the add waits for them last of all)
+    h->copy_pending_seq = src && !has_dirs ? F.seq : 0;
     // (the span's end goes in behind the launch at once: an event recorded after the verdict has come back would count the host's turn as
     // the device's; whatever the add enqueues later — candidate discovery, a grid that is not kept back — records it again, behind itself)
     if (h->chain_add_open) { PISCES_HIP_CHECK(h, hipEventRecord(h->ev_chain[1], h->stream)); h->chain_enqueued_since = false; }
@@ -531,10 +574,11 @@ static int32_t store_device_checks(PiscesHip* h, uint8_t* d, const StageLayout& 
         // (per-base directions are checked by the stream role, which the verdict does not wait for: such a batch waits for the whole launch)
         for (int64_t spin = 0; !has_dirs && !(seen = (*ready == F.seq)); spin++) {
             if ((spin & 1023) == 1023 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(200)) break;
-            __builtin_ia32_pause();
+            cpu_relax();
         }
         std::atomic_thread_fence(std::memory_order_acquire);
         if (!seen) {
+            h->copy_pending_seq = 0;   // (the whole launch is waited for)
             PISCES_HIP_CHECK(h, hipStreamSynchronize(h->stream));
             // (the launch is over: its verdict is there, or the launch is broken — never a verdict of an earlier launch)
             if (*ready != F.seq) return fail(h, PISCES_E_DEVICE, "add_reads: the launch that checks the batch ended without its verdict");
@@ -1021,8 +1065,11 @@ int32_t pisces_hip_add_device_reads(PiscesHip* h, const PiscesReadBatch* batch, 
     if (rc == PISCES_OK) rc = store_device_checks(h, d, L, nr, n_cig, n_seq, has_dirs, has_deldirs, count_indels, &found_slots, &found_pool, touched, &max_key, &min_position,
                                                   batch, shaped ? &shape : nullptr);
     prof_a.reset(new HostTimer(h->prof_on ? &h->prof[14] : nullptr));
-    return store_finish_add(h, pl, rc, d, L, nr, n_cig, n_seq, has_dirs, has_deldirs, find_on_device, found_slots, found_pool, nullptr, touched, max_key, min_position,
-                            shaped ? &shape : nullptr);
+    rc = store_finish_add(h, pl, rc, d, L, nr, n_cig, n_seq, has_dirs, has_deldirs, find_on_device, found_slots, found_pool, nullptr, touched, max_key, min_position,
+                          shaped ? &shape : nullptr);
+    // (the header's promise: the caller's arrays have been read when the call returns — a refused batch included, whose path waited for the stream)
+    { int32_t rcw = store_wait_copied(h); if (rc == PISCES_OK) rc = rcw; }
+    return rc;
     });
 }
 

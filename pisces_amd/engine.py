@@ -169,7 +169,9 @@ class HipVariantCaller:
 
     def AddDeviceReads(self, reads, amplicon_ids=None):
         """pisces_hip_add_device_reads: IStateManager.AddAlleleCounts for a batch that lies in device memory.  `reads`: a DeviceReadBatch
-        (torch tensors on the handle's device), or an _abi.ReadBatch whose arrays are copied there first (test plumbing)."""
+        (torch tensors on the handle's device), or an _abi.ReadBatch whose arrays are copied there first (test plumbing).  The library
+        has read the last byte of the tensors when the call returns (pisces_hip.h): the caller may overwrite or free them at once, on any
+        stream — which is what lets the temporaries of the second form go back to torch's allocator here."""
         b = reads if isinstance(reads, DeviceReadBatch) else DeviceReadBatch.from_host(reads if isinstance(reads, _abi.ReadBatch) else _abi.ReadBatch(reads),
                                                                                        f"cuda:{self.device}")
         b.synchronize()
