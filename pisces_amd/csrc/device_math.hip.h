@@ -15,7 +15,7 @@
 
 namespace pisces {
 
-// Constants the host evaluates once per handle (so host and device agree on them bit for bit).
+// Constants the host evaluates once per handle (so host and device agree on them bit for bit), and the few values a launch sets for itself.
 struct DeviceParams {
     int32_t min_bq, noise_level, max_vq, min_vq, vq_filter, min_cov, low_depth_filter;
     int32_t min_gq, max_gq, low_gq_filter, sb_model, filter_single_strand, include_ref, emit_zero_cov;
@@ -33,8 +33,8 @@ struct DeviceParams {
     // the call phase would run (build_gq_tail_kernel), so a hit is bit-identical to the evaluation it replaces.
     const double* gq_tail;
     int32_t gq_tail_a, gq_tail_cov;
-    int32_t refs_only;   // MNV calling on: SNV candidates come from the read walk, the tile kernels emit Reference records only
-    int32_t variants_only;   // a counting launch over loci OUTSIDE the interval set (pisces_hip_set_exact_total_called): no Reference records, the variants' IsCallable only
+    int32_t refs_only;   // set by the launch: SNV candidates come from the read walk, the tile kernels emit Reference records only
+    int32_t variants_only;   // set by the launch: a counting launch over loci OUTSIDE the interval set (pisces_hip_set_exact_total_called): no Reference records, the variants' IsCallable only
     // Memo tables of the call phase, all filled once per handle BY THE DEVICE with the very functions they stand in for
     // (build_call_tables_kernel), so a hit is bit-identical to the evaluation it replaces; `tab_cov` columns (coverage) each:
     //   vq_tab[k * tab_cov + cov]  = poisson_qscore(k, cov)                                    1 <= k < vq_tab_k   (NoiseModel.Flat)
@@ -49,20 +49,20 @@ struct DeviceParams {
     // MNV calling on, split form (surface_flush.inc.h): SNV candidates are the allele counts — as with MNV calling off — everywhere but on
     // the DIRTY loci, where candidates of the read walk decide (an MNV candidate spans the locus and has taken bases out of the SNVs there,
     // an open-ended SNV candidate sits on it, a failed MNV's leftovers landed on it, ...): there the tile kernels emit the Reference
-    // record only and the variants come from the candidate kernel.  Bit (position - dirty_first) of dirty_bits; nullptr: no locus is dirty.
+    // record only and the variants come from the candidate kernel.  Bit (position - dirty_first) of dirty_bits; nullptr: no locus is dirty.  Set by the launch.
     const uint32_t* dirty_bits;
     int32_t dirty_first, dirty_n;
     // The folded counts int32[position - folded_first][6][3] of every locus the launch walks (anchor bins added up, low-quality bases
-    // under N: what the call phase itself reads), for the candidate kernel of the same flush; nullptr: not wanted.
+    // under N: what the call phase itself reads), for the candidate kernel of the same flush; nullptr: not wanted.  Set by the one launch that writes them.
     int32_t* folded_out;
     int32_t folded_first, folded_n;
 };
 
-// The fields of DeviceParams that change after pisces_hip_create and that a launch of call_tiles_wave_kernel can see changed — per flush
-// (the dirty-locus bitmap, refs_only) or per launch (variants_only, totals).  The kernel takes these by value, behind its eight launch
-// values, and reads every other field from the handle's device copy of DeviceParams, which is written once when the handle is created
-// and never again.  (The folded-count window, the other per-flush part of DeviceParams, is only ever set around a launch of
-// call_store_tiles_kernel: this kernel is never asked for it, and tile_launch_params() says so.)
+// The fields of DeviceParams that a launch sets for itself and that call_tiles_wave_kernel can be launched with: a flush's own (the
+// dirty-locus bitmap, refs_only: FlushScope, surface_flush.inc.h) or one launch's (variants_only, totals).  The handle keeps constants
+// only — host copy and device copy are written by pisces_hip_create and never again — and the host puts each launch's DeviceParams
+// together from them and these values.  The kernel takes these by value, behind its eight launch values, and reads every other field from
+// the device copy.  (The folded-count window is call_store_tiles_kernel's alone: this type cannot carry it.)
 struct TileLaunchParams {
     unsigned long long* totals;
     const uint32_t* dirty_bits;

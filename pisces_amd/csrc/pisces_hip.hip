@@ -287,7 +287,14 @@ struct ReadSegment {
 
 struct PiscesHip {
     PiscesHipConfig cfg;
-    DeviceParams P;
+    // The constants of the call phase.  pisces_hip_create writes them (through params_at_create()) and nothing does after it: every other
+    // reader has the const view P, d_params is their device copy, and what a flush or a single launch changes is put together for that
+    // launch (FlushScope and launch_params, surface_flush.inc.h).
+    const DeviceParams& P = params_;
+    DeviceParams& params_at_create() { return params_; }
+private:
+    DeviceParams params_;
+public:
     int device = 0;
     hipStream_t stream = nullptr;
     // pisces_hip_call_tiles_batched: lanes that independent batches are spread over, created on first use
@@ -351,9 +358,8 @@ struct PiscesHip {
     DeviceBuf<double> d_sb_tab;
     DeviceBuf<double> d_sb0_tab;
     DeviceBuf<int16_t> d_gq_cap;
-    // Device copy of P as pisces_hip_create leaves it: where call_tiles_wave_kernel reads every field that does not change afterwards
-    // (configuration, table pointers).  The fields that do change (TileLaunchParams) travel with each launch, so this copy is never
-    // rewritten; code that makes another field of P changeable has to refresh it in stream order on h->stream.
+    // Device copy of P, written by pisces_hip_create and never again: where call_tiles_wave_kernel reads every field but the ones that
+    // travel with each launch (TileLaunchParams).
     DeviceBuf<DeviceParams> d_params;
     int n_cus = 256;
     void* comm = nullptr;           // ncclComm_t of the summary reduce (pisces_hip_comm_init), or nullptr
@@ -529,12 +535,10 @@ struct PiscesHip {
     int64_t snv_ub = 0;                       // groups in d_snv[snv_cur], an upper bound while a batch's gather is in flight
     DeviceBuf<SnvGroup> d_snv_sel;
     SnvGroup* h_snv_sel = nullptr;            // pinned: {selected, kept} counts (16 bytes), then the first kSnvSpec selected groups
-    DeviceBuf<uint32_t> d_dirty;
-    std::vector<uint32_t> dirty_host;
-    std::vector<HostCandidate> split_selected;   // the SNV groups of the current batch's dirty loci (split_prepare -> call_spanning), by position
+    DeviceBuf<uint32_t> d_dirty;              // a flush's dirty-locus bit map (FlushScope says which positions) ...
+    std::vector<uint32_t> dirty_words;        // ... and the storage of its host copy, kept for its capacity: read through FlushScope::dirty_host only
     uint32_t batch_seq = 0, host_seq = 0;     // arrival stamps: (batch_seq << 32) | record index, host-side additions behind the batch's records
-    DeviceBuf<int32_t> d_folded;              // the folded counts the flush's tile kernel leaves for the candidate kernel (DeviceParams::folded_out)
-    struct { bool valid = false; int32_t lo = 0, hi = 0; } fold;   // the positions d_folded holds (the tile kernels of this flush went first)
+    DeviceBuf<int32_t> d_folded;              // the folded counts the flush's tile kernel leaves for the candidate kernel (DeviceParams::folded_out; FlushScope::fold says which positions)
     DeviceBuf<PiscesTile> d_span_tiles;       // the 64-locus tiles whose anchor-resolved counts the candidate kernel reads (call_spanning)
     DeviceBuf<long long> d_row_idx;           // gather_count_rows_kernel
     DeviceBuf<int32_t> d_rows;
@@ -919,7 +923,8 @@ int32_t pisces_hip_create(const PiscesHipConfig* cfg, int32_t device, PiscesHip*
     PiscesHip* h = new PiscesHip();
     h->cfg = *cfg;
     h->cfg.tile_loci = kTile;
-    h->P = make_params(h->cfg);
+    DeviceParams& P = h->params_at_create();   // (the one place that writes them)
+    P = make_params(h->cfg);
     adaptive_default_params(h->adaptive);
     h->device = device;
     if ((e = hipSetDevice(device)) != hipSuccess || (e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking)) != hipSuccess ||
@@ -935,7 +940,7 @@ int32_t pisces_hip_create(const PiscesHipConfig* cfg, int32_t device, PiscesHip*
         pisces_hip_destroy(h);
         return PISCES_E_DEVICE;
     }
-    h->P.totals = h->d_totals.p;
+    P.totals = h->d_totals.p;
     {
         hipDeviceProp_t prop;
         if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) h->n_cus = prop.multiProcessorCount;
@@ -976,8 +981,8 @@ int32_t pisces_hip_create(const PiscesHipConfig* cfg, int32_t device, PiscesHip*
             pisces_hip_destroy(h);
             return PISCES_E_DEVICE;
         }
-        h->P.q_to_p_lut = h->d_qlut.p;
-        h->P.q_to_p_n = n;
+        P.q_to_p_lut = h->d_qlut.p;
+        P.q_to_p_n = n;
     }
     if (h->cfg.noise_model == PISCES_NOISE_WINDOW) {
         if ((e = ensure_quality_lut(h)) != hipSuccess) {
@@ -999,10 +1004,10 @@ int32_t pisces_hip_create(const PiscesHipConfig* cfg, int32_t device, PiscesHip*
     std::unique_ptr<TableSet> kept(tables_by_default ? take_tables(h->cfg, h->device) : nullptr);
     if (kept) {   // the tables a destroyed handle of this configuration left (the sizes are the constants below)
         h->d_gq_tail.swap(kept->gq_tail); h->d_vq_tab.swap(kept->vq_tab); h->d_sb_tab.swap(kept->sb_tab); h->d_sb0_tab.swap(kept->sb0_tab); h->d_gq_cap.swap(kept->gq_cap);
-        h->P.gq_tail = h->d_gq_tail.p; h->P.gq_tail_a = 32; h->P.gq_tail_cov = 8192;
-        h->P.vq_tab = h->d_vq_tab.p; h->P.sb_tab = h->d_sb_tab.p; h->P.sb0_tab = h->d_sb0_tab.p; h->P.gq_cap = h->d_gq_cap.p;
-        h->P.vq_tab_k = h->P.sb_tab_k = 256;
-        h->P.tab_cov = 8192;
+        P.gq_tail = h->d_gq_tail.p; P.gq_tail_a = 32; P.gq_tail_cov = 8192;
+        P.vq_tab = h->d_vq_tab.p; P.sb_tab = h->d_sb_tab.p; P.sb0_tab = h->d_sb0_tab.p; P.gq_cap = h->d_gq_cap.p;
+        P.vq_tab_k = P.sb_tab_k = 256;
+        P.tab_cov = 8192;
         h->tables_shareable = true;
     }
     if (!kept && !getenv("PISCES_HIP_NO_GQ_TABLE")) {
@@ -1014,15 +1019,15 @@ int32_t pisces_hip_create(const PiscesHipConfig* cfg, int32_t device, PiscesHip*
             return PISCES_E_DEVICE;
         }
         hipLaunchKernelGGL(build_gq_tail_kernel, dim3((unsigned)((n_a * n_cov + 255) / 256)), dim3(256), 0, h->stream, h->d_gq_tail.p,
-                           n_a, n_cov, h->P.target_lod);
+                           n_a, n_cov, P.target_lod);
         if ((e = hipGetLastError()) != hipSuccess || (e = hipStreamSynchronize(h->stream)) != hipSuccess) {
             g_create_error = std::string("pisces_hip_create: ") + hipGetErrorString(e);
             pisces_hip_destroy(h);
             return PISCES_E_DEVICE;
         }
-        h->P.gq_tail = h->d_gq_tail.p;
-        h->P.gq_tail_a = n_a;
-        h->P.gq_tail_cov = n_cov;
+        P.gq_tail = h->d_gq_tail.p;
+        P.gq_tail_a = n_a;
+        P.gq_tail_cov = n_cov;
     }
     if (!kept && !getenv("PISCES_HIP_NO_CALL_TABLES") && h->cfg.noise_model == PISCES_NOISE_FLAT && h->cfg.strand_bias_model != PISCES_SB_DIPLOID &&
         h->cfg.max_variant_qscore <= 32767 && h->cfg.max_genotype_qscore <= 32767 && h->cfg.min_genotype_qscore >= -32768) {
@@ -1032,31 +1037,31 @@ int32_t pisces_hip_create(const PiscesHipConfig* cfg, int32_t device, PiscesHip*
         const int32_t n_k = 256, n_cov = 8192;
         if ((e = h->d_vq_tab.reserve((size_t)n_k * n_cov)) != hipSuccess || (e = h->d_sb_tab.reserve((size_t)n_k * n_cov)) != hipSuccess ||
             (e = h->d_sb0_tab.reserve((size_t)n_cov)) != hipSuccess ||
-            (h->P.gq_tail && (e = h->d_gq_cap.reserve((size_t)h->P.gq_tail_a * h->P.gq_tail_cov)) != hipSuccess)) {
+            (P.gq_tail && (e = h->d_gq_cap.reserve((size_t)P.gq_tail_a * P.gq_tail_cov)) != hipSuccess)) {
             g_create_error = std::string("pisces_hip_create: ") + hipGetErrorString(e);
             pisces_hip_destroy(h);
             return PISCES_E_DEVICE;
         }
         const unsigned nb = (unsigned)(((size_t)n_k * n_cov + 255) / 256);
-        hipLaunchKernelGGL(build_vq_tab_kernel, dim3(nb), dim3(256), 0, h->stream, h->d_vq_tab.p, n_k, n_cov, h->P);
-        hipLaunchKernelGGL(build_sb_tab_kernel, dim3(nb), dim3(256), 0, h->stream, h->d_sb_tab.p, h->d_sb0_tab.p, n_k, n_cov, h->P);
-        if (h->P.gq_tail)
-            hipLaunchKernelGGL(build_gq_cap_kernel, dim3((unsigned)((h->P.gq_tail_a * h->P.gq_tail_cov + 255) / 256)), dim3(256), 0, h->stream,
-                               h->d_gq_cap.p, h->P.gq_tail, h->P.gq_tail_a, h->P.gq_tail_cov, h->P);
+        hipLaunchKernelGGL(build_vq_tab_kernel, dim3(nb), dim3(256), 0, h->stream, h->d_vq_tab.p, n_k, n_cov, P);
+        hipLaunchKernelGGL(build_sb_tab_kernel, dim3(nb), dim3(256), 0, h->stream, h->d_sb_tab.p, h->d_sb0_tab.p, n_k, n_cov, P);
+        if (P.gq_tail)
+            hipLaunchKernelGGL(build_gq_cap_kernel, dim3((unsigned)((P.gq_tail_a * P.gq_tail_cov + 255) / 256)), dim3(256), 0, h->stream,
+                               h->d_gq_cap.p, P.gq_tail, P.gq_tail_a, P.gq_tail_cov, P);
         if ((e = hipGetLastError()) != hipSuccess || (e = hipStreamSynchronize(h->stream)) != hipSuccess) {
             g_create_error = std::string("pisces_hip_create: ") + hipGetErrorString(e);
             pisces_hip_destroy(h);
             return PISCES_E_DEVICE;
         }
-        h->P.vq_tab = h->d_vq_tab.p;
-        h->P.sb_tab = h->d_sb_tab.p;
-        h->P.sb0_tab = h->d_sb0_tab.p;
-        h->P.gq_cap = h->P.gq_tail ? h->d_gq_cap.p : nullptr;
-        h->P.vq_tab_k = h->P.sb_tab_k = n_k;
-        h->P.tab_cov = n_cov;
-        h->tables_shareable = tables_by_default && h->P.gq_tail != nullptr;
+        P.vq_tab = h->d_vq_tab.p;
+        P.sb_tab = h->d_sb_tab.p;
+        P.sb0_tab = h->d_sb0_tab.p;
+        P.gq_cap = P.gq_tail ? h->d_gq_cap.p : nullptr;
+        P.vq_tab_k = P.sb_tab_k = n_k;
+        P.tab_cov = n_cov;
+        h->tables_shareable = tables_by_default && P.gq_tail != nullptr;
     }
-    if ((e = h->d_params.reserve(1)) != hipSuccess || (e = hipMemcpy(h->d_params.p, &h->P, sizeof(DeviceParams), hipMemcpyHostToDevice)) != hipSuccess) {
+    if ((e = h->d_params.reserve(1)) != hipSuccess || (e = hipMemcpy(h->d_params.p, &P, sizeof(DeviceParams), hipMemcpyHostToDevice)) != hipSuccess) {
         g_create_error = std::string("pisces_hip_create: ") + hipGetErrorString(e);
         pisces_hip_destroy(h);
         return PISCES_E_DEVICE;

@@ -32,7 +32,7 @@ int32_t pisces_hip_call_tiles(PiscesHip* h, const uint32_t* d_tuples, const Pisc
         h->ring_used++;
     }
     if (n_tiles > 0) {
-        PISCES_HIP_CHECK(h, launch_call_tiles(h, s, d_tuples, d_tiles, n_tiles, d_ref_bases, ref_start_position, ref_length, d_records, d_tile_results, e0, e1));
+        PISCES_HIP_CHECK(h, launch_call_tiles(h, s, tile_launch_params(h->P), d_tuples, d_tiles, n_tiles, d_ref_bases, ref_start_position, ref_length, d_records, d_tile_results, e0, e1));
         // PloidyModel.DiploidByThresholding / Haploid / DiploidByAdaptiveGT: a pass over the slots
         if (germline(h)) launch_genotype_loci(h, s, d_records, d_tile_results, n_tiles, h->d_posteriors);
     } else if (e0) {
@@ -92,7 +92,7 @@ int32_t pisces_hip_call_tiles_batched(PiscesHip* h, const PiscesTileBatch* batch
     for (int32_t i = 0; i < n_batches; i++) {
         const PiscesTileBatch& b = batches[i];
         if (b.n_tiles == 0) continue;
-        PISCES_HIP_CHECK(h, launch_call_tiles(h, h->lane[i % lanes], b.d_tuples, b.d_tiles, b.n_tiles, b.d_ref_bases, b.ref_start_position,
+        PISCES_HIP_CHECK(h, launch_call_tiles(h, h->lane[i % lanes], tile_launch_params(h->P), b.d_tuples, b.d_tiles, b.n_tiles, b.d_ref_bases, b.ref_start_position,
                                               b.ref_length, b.d_records, b.d_tile_results));
         if (germline(h)) launch_genotype_loci(h, h->lane[i % lanes], b.d_records, b.d_tile_results, b.n_tiles);
     }
@@ -137,7 +137,7 @@ int32_t pisces_hip_call_tiles_graph_build(PiscesHip* h, const PiscesTileBatch* b
         // (event records of a capture become event-record nodes: the stamps are taken when the replay reaches them)
         if (e0) e = hipEventRecord(e0, h->stream);
         if (e == hipSuccess)
-            e = launch_call_tiles(h, h->stream, b.d_tuples, b.d_tiles, b.n_tiles, b.d_ref_bases, b.ref_start_position, b.ref_length, b.d_records,
+            e = launch_call_tiles(h, h->stream, tile_launch_params(h->P), b.d_tuples, b.d_tiles, b.n_tiles, b.d_ref_bases, b.ref_start_position, b.ref_length, b.d_records,
                                   b.d_tile_results);
         if (e == hipSuccess && germline(h)) launch_genotype_loci(h, h->stream, b.d_records, b.d_tile_results, b.n_tiles);
         if (e == hipSuccess && e1) e = hipEventRecord(e1, h->stream);

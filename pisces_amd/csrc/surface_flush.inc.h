@@ -170,10 +170,23 @@ static int32_t drop_blocks(PiscesHip* h, const std::vector<int32_t>& keys)
     return PISCES_OK;
 }
 
+// The parameters of one launch: the handle's constants with the launch's own values in place (the host's side of apply_launch_params).
+// The folded-count window is not among those values: the one launch that writes it sets it on what this returns (call_blocks_enqueue).
+static DeviceParams launch_params(const PiscesHip* h, const TileLaunchParams& L)
+{
+    DeviceParams P = h->P;
+    P.totals = L.totals;
+    P.dirty_bits = L.dirty_bits; P.dirty_first = L.dirty_first; P.dirty_n = L.dirty_n;
+    P.refs_only = L.refs_only; P.variants_only = L.variants_only;
+    return P;
+}
+
 // launches the fused tuples -> histogram -> call kernel on stream s
+// L: what this launch sets of the parameters — a flush's (FlushScope::launch_values), or tile_launch_params(h->P), the handle's constants,
+// for the direct surface; the wave forms take it as it is, the other kernels as launch_params(h, L)
 // e0 / e1 (optional): HIP events bound to the dispatch itself (hipExtLaunchKernel): their timestamps are the kernel's own
 // start and end, not the arrival of separate marker packets before and after it.
-static hipError_t launch_call_tiles(PiscesHip* h, hipStream_t s, const uint32_t* d_tuples, const PiscesTile* d_tiles, int32_t n_tiles,
+static hipError_t launch_call_tiles(PiscesHip* h, hipStream_t s, const TileLaunchParams& L, const uint32_t* d_tuples, const PiscesTile* d_tiles, int32_t n_tiles,
                               const uint8_t* d_ref, int32_t ref_start, int64_t ref_len, PiscesCalledAllele* d_records,
                               PiscesTileResult* d_tr, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr)
 {
@@ -185,7 +198,7 @@ static hipError_t launch_call_tiles(PiscesHip* h, hipStream_t s, const uint32_t*
         hipError_t er = accumulate_tiles(h, s, d_tuples, d_tiles, n_tiles, true);
         if (er != hipSuccess) return er;
         hipLaunchKernelGGL(call_counts_kernel, dim3((unsigned)n_tiles), dim3(kBlock), 0, s, h->d_counts.p, (const uint32_t*)nullptr, d_tiles, n_tiles,
-                           d_ref, ref_start, ref_len, d_records, d_tr, h->P, h->d_sumq.p);
+                           d_ref, ref_start, ref_len, d_records, d_tr, launch_params(h, L), h->d_sumq.p);
         if (e1) (void)hipEventRecord(e1, s);
         return hipSuccess;
     }
@@ -196,8 +209,6 @@ static hipError_t launch_call_tiles(PiscesHip* h, hipStream_t s, const uint32_t*
         // to ~8 k tiles per launch (56 % vs 49 % at 2048 tiles, 62 % vs 60 % at 8192); beyond that tiles interleave on their
         // own and one wave per tile (no spills, 12 tiles per CU) streams better (68.5 % vs 66 % at 15 625 tiles).
         // (what changes per flush or per launch travels by value; every other parameter is the handle's device copy, written at create)
-        if (h->P.folded_out) return hipErrorInvalidValue;   // (the folded counts are call_store_tiles_kernel's: TileLaunchParams does not carry them)
-        const TileLaunchParams L = tile_launch_params(h->P);
         const bool two = h->kernel_variant == 3 || (h->kernel_variant == 4 && (int64_t)n_tiles <= (int64_t)h->n_cus * 32);
         // (without events the plain launch: it is what a stream capture records as a kernel node)
         if (!two && !e0 && !e1)
@@ -215,7 +226,7 @@ static hipError_t launch_call_tiles(PiscesHip* h, hipStream_t s, const uint32_t*
         return hipSuccess;
     }
     hipExtLaunchKernelGGL(call_tiles_kernel, dim3((unsigned)n_tiles), dim3(kBlock), 0, s, e0, e1, 0u, d_tuples, d_tiles, n_tiles, d_ref,
-                          ref_start, ref_len, d_records, d_tr, h->P);
+                          ref_start, ref_len, d_records, d_tr, launch_params(h, L));
     return hipSuccess;
 }
 
@@ -275,6 +286,85 @@ static int32_t launch_compaction(PiscesHip* h, hipStream_t s, const PiscesCalled
     return PISCES_OK;
 }
 
+// Which way the tile kernels of a batch go: decided in one place (plan_tile_path) for everything that depends on it — the order of a
+// flush's two halves, the launch and its geometry, what pisces_hip_set_exact_total_called can count.
+struct TilePath {
+    bool use_counts = false;   // a gapped-MNV reference count lies in the batch: counts in HBM, call_counts_kernel
+    bool window = false;       // NoiseModel.Window: the same, with the base-quality sums
+    bool store = false;        // the read store (else the observation log)
+    bool fused = false;        // the read store's fused kernel (call_store_tiles_kernel)
+    bool regular = false;      // ... over a run of whole consecutive blocks: the tile geometry travels by value (RegularTiles)
+    bool log_empty = false;
+    bool blocks_first = false; // fused && regular, and the launch may go ahead of the candidates and leave them its folded counts
+    int tile_loci = kTile, tiles_per_block = 0;
+};
+static TilePath plan_tile_path(const PiscesHip* h, const std::vector<int32_t>& keys)
+{
+    TilePath T;
+    const int bs = h->cfg.block_size;
+    T.tiles_per_block = (bs + kTile - 1) / kTile;
+    if (keys.empty()) return T;
+    T.window = h->cfg.noise_model == PISCES_NOISE_WINDOW;
+    for (auto& kv : h->gapped_mnv_ref)
+        if (std::binary_search(keys.begin(), keys.end(), block_key(h, kv.first))) { T.use_counts = true; break; }
+    // the read store calls through call_store_tiles_kernel; configurations that kernel is not compiled for (the Diploid strand-bias model,
+    // the 4-wave development form, a quality threshold above 127) go through the counts in HBM
+    T.store = h->read_path == 1;
+    const bool store_fused = h->kernel_variant >= 2 && h->cfg.strand_bias_model != PISCES_SB_DIPLOID && h->cfg.min_base_call_quality <= 127;
+    T.fused = !T.use_counts && !T.window && T.store && store_fused;
+    T.log_empty = h->log_ub == 0;
+    // A run of consecutive blocks that no interval set clips, nothing in the observation log: the tile geometry goes to the kernel by
+    // value (RegularTiles) — no geometry is made on the host and none uploaded
+    T.regular = T.fused && T.log_empty && h->intervals.empty() && (int64_t)keys.back() - keys.front() + 1 == (int64_t)keys.size() &&
+                (int64_t)keys.size() * T.tiles_per_block < 0x7FFFFF00ll / kSlotsPerTile;
+    // The launch can go first and leave the folded counts for the candidate kernel when they fit, and when the rows are not genotyped per
+    // locus (whether that happens on the device is only known once the candidates have been through)
+    T.blocks_first = T.regular && h->d_ref.p && !germline(h) && (int64_t)keys.size() * bs < (0x7FFFFF00ll / PISCES_FOLDED_PER_LOCUS);
+    // The tiles of a regular run may be of any size up to 64 (RegularTiles::tile_loci).  A launch ends with the CU that was dealt the most
+    // loci — ceil(tiles / CUs) tiles — and 100 blocks on 256 CUs put 7 x 64 = 448 loci on 64 CUs with tiles of 64 but 7 x 59 = 413 with
+    // tiles of 59; measured (round 6, config 2's flush, tools/tile_loci_ab.sh): 64 -> 50.8-51.3 us for the flush's span, 59 -> 51.4,
+    // 56 / 60 / 62 -> 54.5 / 53.2 / 53.8: the trade of tiles inside the kernel has taken that imbalance already.  64 stays; PISCES_HIP_TILE_LOCI forces a size.
+    if (T.regular && h->tile_loci > 0 && h->tile_loci < kTile && (int64_t)keys.size() * ((bs + h->tile_loci - 1) / h->tile_loci) < 0x7FFFFF00ll / kSlotsPerTile) {
+        T.tile_loci = h->tile_loci;
+        T.tiles_per_block = (bs + T.tile_loci - 1) / T.tile_loci;
+    }
+    return T;
+}
+
+// Everything that lives for one flush: a value on the stack of flush_build (of pisces_hip_flush_begin for the asynchronous form), filled
+// by split_prepare and call_blocks_enqueue, read by the launches and the host stages of that flush, gone with it.  The handle keeps none
+// of this: a launch outside a flush (surface_device.inc.h) sees the handle's constants, whatever was flushed before it.
+struct FlushScope {
+    // the dirty loci (split_prepare): bit (position - dirty_first) of the map, on the device and on the host; d_dirty nullptr: no locus is dirty
+    const uint32_t* d_dirty = nullptr;
+    int32_t dirty_first = 0, dirty_n = 0;
+    std::vector<uint32_t>& dirty_host;
+    // DeviceParams::refs_only of this flush's launches: the SNV candidates come from the read walk — but for the split form, whose SNVs
+    // are the allele counts' outside the dirty loci
+    int32_t refs_only;
+    std::vector<HostCandidate> selected;   // the SNV groups of the batch's dirty loci (split_prepare -> call_spanning), by position
+    // the positions whose folded counts the tile kernels' launch left in d_folded (it went ahead of the candidates)
+    struct { bool valid = false; int32_t lo = 0, hi = 0; const int32_t* d_folded = nullptr; } fold;
+    TilePath path;
+
+    explicit FlushScope(PiscesHip* h) : dirty_host(h->dirty_words), refs_only(h->snv_walk ? 1 : 0) {}
+    bool dirty_at(int32_t p) const
+    {
+        const int64_t rel = (int64_t)p - dirty_first;
+        if (!d_dirty || rel < 0 || rel >= dirty_n) return false;
+        return ((dirty_host[(size_t)(rel >> 5)] >> (rel & 31)) & 1u) != 0u;
+    }
+    bool in_fold(int32_t p) const { return fold.valid && p >= fold.lo && p <= fold.hi; }
+    // what a launch of this flush sets of the parameters (launch_params makes the DeviceParams of it)
+    TileLaunchParams launch_values(const PiscesHip* h) const
+    {
+        TileLaunchParams L = tile_launch_params(h->P);
+        L.dirty_bits = d_dirty; L.dirty_first = dirty_first; L.dirty_n = dirty_n;
+        L.refs_only = refs_only;
+        return L;
+    }
+};
+
 // device work of one flush: returns called alleles of `keys` sorted by (position, ref, alt)
 // The device work of one flush in two halves: everything up to the copies into the pinned download buffer is enqueued by
 // call_blocks_enqueue; call_blocks_finish reads what came back once the stream (or an event behind the copies) has been waited for.
@@ -288,9 +378,9 @@ struct CallBlocksInFlight {
     const int32_t* extra = nullptr;   // {records, called} of the counting launch over the off-interval loci (exact TotalNumCalled), or nullptr
 };
 // pisces_hip_set_exact_total_called: the loci of `keys`' blocks that lie OUTSIDE the interval set, through the flush kernel once more with
-// DeviceParams::variants_only (no Reference records; variants exactly as inside the intervals: dirty loci are skipped there and counted by
+// DeviceParams::variants_only and without the running totals (no Reference records; variants exactly as inside the intervals: dirty loci are skipped there and counted by
 // the candidate path, as everywhere), the records dropped, the tiles' n_called summed into pinned memory behind the same wait.
-static int32_t enqueue_off_interval_count(PiscesHip* h, const std::vector<int32_t>& keys, CallBlocksInFlight* st)
+static int32_t enqueue_off_interval_count(PiscesHip* h, const FlushScope& S, const std::vector<int32_t>& keys, CallBlocksInFlight* st)
 {
     const int bs = h->cfg.block_size;
     std::vector<PiscesTile> tiles;
@@ -324,15 +414,11 @@ static int32_t enqueue_off_interval_count(PiscesHip* h, const std::vector<int32_
     PISCES_HIP_CHECK(h, h->d_cnt_x.reserve(4));
     if (!h->h_cnt_x) PISCES_HIP_CHECK(h, host_alloc((void**)&h->h_cnt_x, 64));
     { int32_t rcu = meta_upload(h, h->d_tiles_x.p, tiles.data(), tiles.size() * sizeof(PiscesTile)); if (rcu) return rcu; }
-    const DeviceParams saved = h->P;
-    h->P.variants_only = 1;
-    h->P.totals = nullptr;
-    h->P.folded_out = nullptr;
-    h->P.folded_first = h->P.folded_n = 0;
+    TileLaunchParams L = S.launch_values(h);
+    L.variants_only = 1;
+    L.totals = nullptr;
     const RegularTiles R = {0, bs, (bs + kTile - 1) / kTile, 0};
-    const hipError_t e = launch_call_store_tiles(h, h->stream, nullptr, h->d_tiles_x.p, R, n, h->d_ref.p, 1, h->ref_len, h->d_rec_x.p, h->d_tr_x.p);
-    h->P = saved;
-    PISCES_HIP_CHECK(h, e);
+    PISCES_HIP_CHECK(h, launch_call_store_tiles(h, h->stream, launch_params(h, L), nullptr, h->d_tiles_x.p, R, n, h->d_ref.p, 1, h->ref_len, h->d_rec_x.p, h->d_tr_x.p));
     hipLaunchKernelGGL(scan_tile_counts_kernel, dim3(1), dim3(1024), 0, h->stream, (const PiscesTileResult*)h->d_tr_x.p, n, h->d_off_x.p, h->d_cnt_x.p, h->d_cnt_x.p + 1);
     PISCES_HIP_CHECK(h, hipGetLastError());
     PISCES_HIP_CHECK(h, hipMemcpyAsync(h->h_cnt_x, h->d_cnt_x.p, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
@@ -340,42 +426,21 @@ static int32_t enqueue_off_interval_count(PiscesHip* h, const std::vector<int32_
     return PISCES_OK;
 }
 
+// S.path says which way the tiles go (plan_tile_path of these keys, made by the caller: what is flushed must not have changed since)
 // hole_bound >= 0 (asynchronous flush): the compacted log is made hole_bound slots long (see enqueue_drop)
 // with_folded: the launch — when it is the fused kernel over a run of whole blocks — also leaves the folded counts of every locus it walks
-// in h->d_folded (h->fold says which positions), for the candidate kernel of the same flush
+// in h->d_folded (S.fold says which positions), for the candidate kernel of the same flush
 // genotype_on_device: a diploid / haploid handle's rows are genotyped where they lie (genotype_loci_kernel) before they are compacted:
 // the caller knows that no row of the candidate kernel and no forced allele joins them
-static int32_t call_blocks_enqueue(PiscesHip* h, const std::vector<int32_t>& keys, bool with_drop, int64_t hole_bound, CallBlocksInFlight* st, bool with_folded = false,
-                                   bool genotype_on_device = false)
+static int32_t call_blocks_enqueue(PiscesHip* h, FlushScope& S, const std::vector<int32_t>& keys, bool with_drop, int64_t hole_bound, CallBlocksInFlight* st,
+                                   bool with_folded = false, bool genotype_on_device = false)
 {
     *st = CallBlocksInFlight();
-    h->fold.valid = false;
     if (keys.empty()) return PISCES_OK;
     if (!h->d_ref.p) return fail(h, PISCES_E_STATE, "flush: set_reference has not been called");
-    const bool window = h->cfg.noise_model == PISCES_NOISE_WINDOW;
-    bool use_counts = false;
-    for (auto& kv : h->gapped_mnv_ref)
-        if (std::binary_search(keys.begin(), keys.end(), block_key(h, kv.first))) { use_counts = true; break; }
-    // the read store calls through call_store_tiles_kernel; configurations that kernel is not compiled for (the Diploid strand-bias model,
-    // the 4-wave development form, a quality threshold above 127) go through the counts in HBM
-    const bool store = h->read_path == 1;
-    const bool store_fused = h->kernel_variant >= 2 && h->cfg.strand_bias_model != PISCES_SB_DIPLOID && h->cfg.min_base_call_quality <= 127;
-    const bool fused = !use_counts && !window && store && store_fused;
-    // A run of consecutive blocks that no interval set clips, nothing in the observation log: the tile geometry goes to the kernel by
-    // value (RegularTiles) — no geometry is made on the host and none uploaded
-    const int bs = h->cfg.block_size;
-    int tiles_per_block = (bs + kTile - 1) / kTile;
-    const bool regular = fused && h->log_ub == 0 && h->intervals.empty() && (int64_t)keys.back() - keys.front() + 1 == (int64_t)keys.size() &&
-                         (int64_t)keys.size() * tiles_per_block < 0x7FFFFF00ll / kSlotsPerTile;
-    // The tiles of a regular run may be of any size up to 64 (RegularTiles::tile_loci).  A launch ends with the CU that was dealt the most
-    // loci — ceil(tiles / CUs) tiles — and 100 blocks on 256 CUs put 7 x 64 = 448 loci on 64 CUs with tiles of 64 but 7 x 59 = 413 with
-    // tiles of 59; measured (round 6, config 2's flush, tools/tile_loci_ab.sh): 64 -> 50.8-51.3 us for the flush's span, 59 -> 51.4,
-    // 56 / 60 / 62 -> 54.5 / 53.2 / 53.8: the trade of tiles inside the kernel has taken that imbalance already.  64 stays; PISCES_HIP_TILE_LOCI forces a size.
-    int tile_loci = kTile;
-    if (regular && h->tile_loci > 0 && h->tile_loci < kTile && (int64_t)keys.size() * ((bs + h->tile_loci - 1) / h->tile_loci) < 0x7FFFFF00ll / kSlotsPerTile) {
-        tile_loci = h->tile_loci;
-        tiles_per_block = (bs + tile_loci - 1) / tile_loci;
-    }
+    const TilePath& T = S.path;
+    const bool window = T.window, use_counts = T.use_counts, store = T.store, fused = T.fused, regular = T.regular;
+    const int bs = h->cfg.block_size, tile_loci = T.tile_loci, tiles_per_block = T.tiles_per_block;
     std::vector<PiscesTile> tiles;
     int32_t n_tiles = 0;
     int64_t n_loci_total = 0;
@@ -409,22 +474,21 @@ static int32_t call_blocks_enqueue(PiscesHip* h, const std::vector<int32_t>& key
             e1 = h->ring[2 * slot + 1];
             h->ring_used++;
         }
+        DeviceParams P = launch_params(h, S.launch_values(h));
         if (with_folded && regular) {
             PISCES_HIP_CHECK(h, h->d_folded.reserve((size_t)n_loci_total * PISCES_FOLDED_PER_LOCUS));
-            h->P.folded_out = h->d_folded.p;
-            h->P.folded_first = (keys.front() - 1) * bs + 1;
-            h->P.folded_n = (int32_t)n_loci_total;
-            h->fold.valid = true;
-            h->fold.lo = h->P.folded_first;
-            h->fold.hi = h->P.folded_first + (int32_t)n_loci_total - 1;
+            P.folded_out = h->d_folded.p;
+            P.folded_first = (keys.front() - 1) * bs + 1;
+            P.folded_n = (int32_t)n_loci_total;
+            S.fold.valid = true;
+            S.fold.lo = P.folded_first;
+            S.fold.hi = P.folded_first + (int32_t)n_loci_total - 1;
+            S.fold.d_folded = h->d_folded.p;
         }
-        const hipError_t el = launch_call_store_tiles(h, h->stream, regular ? nullptr : h->d_tuples.p, regular ? nullptr : h->d_tiles.p, R, n_tiles, h->d_ref.p, 1,
-                                                      h->ref_len, h->d_records.p, h->d_tile_results.p, e0, e1);
-        h->P.folded_out = nullptr;
-        h->P.folded_first = h->P.folded_n = 0;
-        PISCES_HIP_CHECK(h, el);
+        PISCES_HIP_CHECK(h, launch_call_store_tiles(h, h->stream, P, regular ? nullptr : h->d_tuples.p, regular ? nullptr : h->d_tiles.p, R, n_tiles, h->d_ref.p, 1,
+                                                    h->ref_len, h->d_records.p, h->d_tile_results.p, e0, e1));
     } else if (!use_counts && !window && !store) {
-        PISCES_HIP_CHECK(h, launch_call_tiles(h, h->stream, h->d_tuples.p, h->d_tiles.p, n_tiles, h->d_ref.p, 1, h->ref_len, h->d_records.p,
+        PISCES_HIP_CHECK(h, launch_call_tiles(h, h->stream, S.launch_values(h), h->d_tuples.p, h->d_tiles.p, n_tiles, h->d_ref.p, 1, h->ref_len, h->d_records.p,
                                               h->d_tile_results.p));
     } else {
         // counts in HBM + AddGappedMnvRefCount adjustments (CoverageCalculator.cs:82-97)
@@ -441,7 +505,7 @@ static int32_t call_blocks_enqueue(PiscesHip* h, const std::vector<int32_t>& key
         { int32_t rcu = meta_upload(h, h->d_gapped.p, g.data(), g.size() * sizeof(uint32_t)); if (rcu) return rcu; }
         PISCES_HIP_CHECK(h, accumulate_tiles(h, h->stream, h->d_tuples.p, h->d_tiles.p, n_tiles, window, true));
         hipLaunchKernelGGL(call_counts_kernel, dim3((unsigned)n_tiles), dim3(kBlock), 0, h->stream, h->d_counts.p, h->d_gapped.p,
-                           h->d_tiles.p, n_tiles, h->d_ref.p, 1, h->ref_len, h->d_records.p, h->d_tile_results.p, h->P,
+                           h->d_tiles.p, n_tiles, h->d_ref.p, 1, h->ref_len, h->d_records.p, h->d_tile_results.p, launch_params(h, S.launch_values(h)),
                            window ? h->d_sumq.p : (const double*)nullptr);
     }
     const bool with_posteriors = genotype_on_device && h->cfg.ploidy == PISCES_PLOIDY_DIPLOID_ADAPTIVE;
@@ -522,29 +586,15 @@ static int32_t call_blocks_enqueue(PiscesHip* h, const std::vector<int32_t>& key
     // get a counting launch of the flush kernel.  A configuration that kernel does not serve cannot give the reference's number: refused
     // here, not answered with the smaller one.
     if (h->exact_total_called && !h->intervals.empty() && !h->snv_walk) {
-        if (!(fused && h->log_ub == 0))
+        if (!(fused && T.log_empty))
             return fail(h, PISCES_E_UNSUPPORTED, "flush: pisces_hip_set_exact_total_called is on, but this configuration does not go through the read store's "
                         "flush kernel (NoiseModel.Window, the Diploid strand-bias model, a gapped-MNV reference count in the flushed blocks, the "
                         "observation-log read path or a base-quality threshold above 127): the off-interval total cannot be counted; switch it off");
-        int32_t rcx = enqueue_off_interval_count(h, keys, st);
+        int32_t rcx = enqueue_off_interval_count(h, S, keys, st);
         if (rcx) return rcx;
     }
     return PISCES_OK;
 }
-// Does a flush of `keys` go through the fused kernel over a run of whole blocks (call_blocks_enqueue's `fused && regular`)?  Then its
-// launch can go first and leave the folded counts for the candidate kernel.
-static bool fused_regular_applies(PiscesHip* h, const std::vector<int32_t>& keys)
-{
-    if (keys.empty() || !h->d_ref.p || h->cfg.noise_model == PISCES_NOISE_WINDOW || h->read_path != 1 || h->log_ub != 0 || !h->intervals.empty()) return false;
-    if (germline(h)) return false;   // (whether the rows are genotyped on the device is only known once the candidates have been through)
-    if (!(h->kernel_variant >= 2 && h->cfg.strand_bias_model != PISCES_SB_DIPLOID && h->cfg.min_base_call_quality <= 127)) return false;
-    for (auto& kv : h->gapped_mnv_ref)
-        if (std::binary_search(keys.begin(), keys.end(), block_key(h, kv.first))) return false;
-    const int tiles_per_block = (h->cfg.block_size + kTile - 1) / kTile;
-    return (int64_t)keys.back() - keys.front() + 1 == (int64_t)keys.size() && (int64_t)keys.size() * tiles_per_block < 0x7FFFFF00ll / kSlotsPerTile &&
-           (int64_t)keys.size() * h->cfg.block_size < (0x7FFFFF00ll / PISCES_FOLDED_PER_LOCUS);
-}
-
 // (after the wait) total: the records; they lie in st.hrec, all of them
 static int32_t call_blocks_finish(PiscesHip* h, const CallBlocksInFlight& st, int32_t* total, int64_t* n_called, unsigned long long* kept)
 {
@@ -894,12 +944,6 @@ static inline bool candidate_is_plain_snv(const PiscesHip* h, const HostCandidat
 {
     return c.category == PISCES_CAT_SNV && c.from_reads && !(h->cfg.collapse != 0 && (c.open_left || c.open_right));
 }
-static inline bool split_dirty_at(const PiscesHip* h, int32_t p)
-{
-    const int64_t rel = (int64_t)p - h->P.dirty_first;
-    if (!h->P.dirty_bits || rel < 0 || rel >= h->P.dirty_n) return false;
-    return ((h->dirty_host[(size_t)(rel >> 5)] >> (rel & 31)) & 1u) != 0u;
-}
 
 // One pass over the SNV store: groups on set bits of `bm` (device, or nullptr) -> `selected`; groups at or below drop_hi are dropped; the
 // rest is kept (compacted into the other buffer).  Waits for the device.
@@ -944,19 +988,11 @@ static int32_t snv_store_sweep(PiscesHip* h, const uint32_t* d_bm, int32_t bm_fi
 
 // The dirty loci of the batch `keys` (and, when alleles of the cleared blocks reach past the last cleared position, of the held blocks up
 // to upTo whose candidates AddCollapsableFromOtherBlocks will bring in), as a bit map on host and device; the SNV groups on them join
-// their blocks' candidates; DeviceParams is set for the tile kernels of this flush.  split_restore() undoes the latter.
+// their blocks' candidates (S.selected); S carries the map and refs_only to the launches of this flush.
 // When the SNVs are the allele counts' (MNV calling off, PiscesHip::snv_walk false) the same bit map marks the few loci where they are
 // not: bases of X / = operations (BlockObs::unwalked) and SNV candidates the host handed in; call_spanning makes those loci's candidates.
-static void split_restore(PiscesHip* h)
+static int32_t split_prepare(PiscesHip* h, FlushScope& S, const std::vector<int32_t>& keys, int32_t up_to_position)
 {
-    h->P.dirty_bits = nullptr;
-    h->P.dirty_first = h->P.dirty_n = 0;
-    h->P.refs_only = h->snv_walk ? 1 : 0;
-}
-static int32_t split_prepare(PiscesHip* h, const std::vector<int32_t>& keys, int32_t up_to_position)
-{
-    split_restore(h);
-    h->split_selected.clear();
     // MNV calling off: the loci with bases of X / = operations that the allele counts hold and no SNV candidate stands for are dirty too
     // (their SNVs are called by call_spanning, from the counts less those bases)
     const bool unwalked_mode = !h->snv_walk;
@@ -973,7 +1009,7 @@ static int32_t split_prepare(PiscesHip* h, const std::vector<int32_t>& keys, int
         }
         if (!some) return PISCES_OK;
     } else {
-        h->P.refs_only = 0;
+        S.refs_only = 0;
     }
     if (keys.empty()) return PISCES_OK;
     const int bs = h->cfg.block_size;
@@ -987,7 +1023,7 @@ static int32_t split_prepare(PiscesHip* h, const std::vector<int32_t>& keys, int
     }
     const int64_t n = hi_bm - lo + 1;
     if (n > 0x7FFFFF00ll) return fail(h, PISCES_E_UNSUPPORTED, "flush: the blocks of one batch span more than 2^31 positions");
-    std::vector<uint32_t>& bm = h->dirty_host;
+    std::vector<uint32_t>& bm = S.dirty_host;
     bm.assign((size_t)((n + 31) / 32), 0u);
     bool any = false;
     auto mark = [&](int64_t a, int64_t b) {   // inclusive positions
@@ -1068,8 +1104,7 @@ static int32_t split_prepare(PiscesHip* h, const std::vector<int32_t>& keys, int
         if (rcs) return rcs;
     }
     // The groups of the batch's own blocks do not become block state: they are flushed with this batch, and call_spanning takes them from
-    // h->split_selected (position order, then order of arrival).  Only the few of held blocks (the AddCollapsable case) join their blocks.
-    h->split_selected.clear();
+    // S.selected (position order, then order of arrival).  Only the few of held blocks (the AddCollapsable case) join their blocks.
     if (!selected.empty()) {
         std::sort(selected.begin(), selected.end(), [](const SnvGroup& a, const SnvGroup& b) {
             if (a.position != b.position) return a.position < b.position;
@@ -1077,7 +1112,7 @@ static int32_t split_prepare(PiscesHip* h, const std::vector<int32_t>& keys, int
             return a.first < b.first;
         });
         std::vector<int32_t> touched;
-        h->split_selected.reserve(selected.size());
+        S.selected.reserve(selected.size());
         for (const SnvGroup& g : selected) {
             if (g.position < 1 || (int64_t)g.position > h->ref_len) continue;
             HostCandidate c;
@@ -1088,7 +1123,7 @@ static int32_t split_prepare(PiscesHip* h, const std::vector<int32_t>& keys, int
             for (int d = 0; d < 3; d++) { c.support_by_dir[d] = g.sup[d]; c.well_anchored_by_dir[d] = g.anch[d]; }
             c.stamp = ((uint64_t)g.batch << 32) | (uint64_t)g.first;
             c.from_reads = true;
-            if ((int64_t)g.position <= hi) { h->split_selected.push_back(std::move(c)); continue; }
+            if ((int64_t)g.position <= hi) { S.selected.push_back(std::move(c)); continue; }
             add_candidate(h, c);
             touched.push_back(block_key(h, g.position));
         }
@@ -1098,9 +1133,9 @@ static int32_t split_prepare(PiscesHip* h, const std::vector<int32_t>& keys, int
         h->last_block = nullptr;
     }
     if (any) {
-        h->P.dirty_bits = h->d_dirty.p;
-        h->P.dirty_first = (int32_t)lo;
-        h->P.dirty_n = (int32_t)n;
+        S.d_dirty = h->d_dirty.p;
+        S.dirty_first = (int32_t)lo;
+        S.dirty_n = (int32_t)n;
     }
     return PISCES_OK;
 }
@@ -1108,6 +1143,7 @@ static int32_t split_prepare(PiscesHip* h, const std::vector<int32_t>& keys, int
 // What the stages of call_spanning share: the batch's candidates, the loci whose counts they read and where those counts lie.
 struct SpanBatch {
     PiscesHip* h;
+    const FlushScope* scope;                 // the flush's dirty loci, selected SNV groups, folded window and launch values
     const std::vector<int32_t>* keys;        // the cleared blocks (ascending)
     int32_t up_to_position;
     bool blocks_first;
@@ -1115,10 +1151,9 @@ struct SpanBatch {
     int32_t max_cleared = -1;                // >= 0: candidates of held blocks joined the batch (AddCollapsableFromOtherBlocks)
     std::vector<BlockObs::Unwalked> unw;     // MNV calling off: bases of X / = operations no SNV candidate stands for, by (position, base)
     // where the candidates' counts lie: the folded counts of the tile kernels' launch, or the tensor over `tiles`
-    bool fold_ok = false, sparse_tiles = false;
+    bool sparse_tiles = false;
     std::vector<PiscesTile> tiles;
     std::vector<int32_t> bkeys, tile_starts;   // the tensor's blocks (observation log) / 64-locus tiles (read store)
-    const int32_t* d_folded = nullptr;
     bool counts_missing = false;
     // the gathered count rows the host reads (collapser frequencies, reallocator, SNV support)
     const int32_t* host_counts = nullptr;
@@ -1155,7 +1190,6 @@ static int32_t unwalked_of(const SpanBatch& B, int32_t position, char alt, int d
     return (it != B.unw.end() && it->position == position && it->alt == (uint8_t)alt) ? it->sup[d] : 0;
 }
 
-static bool in_fold(const SpanBatch& B, int32_t p) { return B.fold_ok && p >= B.h->fold.lo && p <= B.h->fold.hi; }
 static int32_t tile_start_of(const SpanBatch& B, int32_t p)
 {
     const int bs = B.h->cfg.block_size;
@@ -1168,7 +1202,7 @@ static int64_t locus_index(SpanBatch& B, int32_t p, bool may_fold = true)
 {
     PiscesHip* h = B.h;
     if (p <= 0) return -1;
-    if (may_fold && in_fold(B, p)) return -((int64_t)(p - h->fold.lo) + 2);   // the folded counts of the tile kernels' launch
+    if (may_fold && B.scope->in_fold(p)) return -((int64_t)(p - B.scope->fold.lo) + 2);   // the folded counts of the tile kernels' launch
     const int32_t k = block_key(h, p);
     if (!h->blocks.count(k)) return -1;   // no block: no counts (RegionStateManager.cs:222-226)
     if (B.sparse_tiles) {
@@ -1285,17 +1319,18 @@ static void span_gather_candidates(SpanBatch& B)
         const size_t first = work.size();
         for (auto& c : h->blocks[key].cands) {
             // (split form of MNV calling: a fully anchored SNV of the read walk on a locus that is not dirty is the tile kernels' to call)
-            if (h->mnv_split && candidate_is_plain_snv(h, c) && !split_dirty_at(h, c.position)) continue;
+            if (h->mnv_split && candidate_is_plain_snv(h, c) && !B.scope->dirty_at(c.position)) continue;
             work.push_back(c);
         }
         // the SNV groups of the block's dirty loci, taken from the device's store for this flush (split_prepare): they go where their
         // arrival puts them among the block's candidates, and a group equal to a candidate that is there already is merged into it
         // (RegionState.AddCandidate, RegionState.cs:114-137)
         bool extra = false;
-        if (h->mnv_split && !h->split_selected.empty()) {
+        const std::vector<HostCandidate>& selected = B.scope->selected;
+        if (h->mnv_split && !selected.empty()) {
             const int32_t b0 = (key - 1) * h->cfg.block_size + 1, b1 = key * h->cfg.block_size;
-            auto lo = std::lower_bound(h->split_selected.begin(), h->split_selected.end(), b0, [](const HostCandidate& c, int32_t p) { return c.position < p; });
-            for (; lo != h->split_selected.end() && lo->position <= b1; ++lo) { work.push_back(*lo); extra = true; }
+            auto lo = std::lower_bound(selected.begin(), selected.end(), b0, [](const HostCandidate& c, int32_t p) { return c.position < p; });
+            for (; lo != selected.end() && lo->position <= b1; ++lo) { work.push_back(*lo); extra = true; }
         }
         if (!extra) {
             std::stable_sort(work.begin() + (std::ptrdiff_t)first, work.end(), [](const HostCandidate& x, const HostCandidate& y) { return x.position < y.position; });
@@ -1362,7 +1397,7 @@ static void span_gather_unwalked(SpanBatch& B)
         unw.insert(unw.end(), u.begin(), u.end());
     }
     for (auto& c : B.work)   // an SNV candidate the host handed in: its locus is dirty; the other bases of the locus are made later, from the counts
-        if (c.category == PISCES_CAT_SNV && split_dirty_at(h, c.position) && c.alt.size() == 1 && in_batch(B, c.position))
+        if (c.category == PISCES_CAT_SNV && B.scope->dirty_at(c.position) && c.alt.size() == 1 && in_batch(B, c.position))
             unw.push_back({c.position, (uint8_t)c.alt[0], {0, 0, 0}});
     if (B.max_cleared >= 0) {   // (SNV candidates of held blocks that joined the batch — forced ones: what the reads so far show at their positions)
         std::vector<int32_t> seen;
@@ -1385,18 +1420,17 @@ static void span_gather_unwalked(SpanBatch& B)
 }
 
 // ---- where the candidates' counts come from (kernels.hip.h CountsView).  Point alleles, MNVs and deletions add up all anchor bins of a
-// cell: when the flush's tile kernel has run over these blocks already it left exactly those sums for every locus (h->fold), and no
+// cell: when the flush's tile kernel has run over these blocks already it left exactly those sums for every locus (FlushScope::fold), and no
 // second walk over the reads is needed for them.  What is left — insertions (their coverage looks at the bins), loci outside that
 // launch (an allele that ends in a held block), or everything when the tile kernels come later — is accumulated into the tensor, for
 // the 64-locus tiles those loci lie in only (the read store; with an observation log: the whole blocks, bucketed as they always were).
 static std::vector<int32_t> span_tensor_positions(SpanBatch& B)
 {
     PiscesHip* h = B.h;
-    B.fold_ok = B.blocks_first && h->fold.valid;
     B.sparse_tiles = h->read_path == 1 && h->log_ub == 0;
     std::vector<int32_t> need_pos;   // positions whose counts must be in the tensor
     auto need = [&](int32_t p, bool may_fold) {
-        if (p > 0 && !(may_fold && in_fold(B, p)) && h->blocks.count(block_key(h, p))) need_pos.push_back(p);
+        if (p > 0 && !(may_fold && B.scope->in_fold(p)) && h->blocks.count(block_key(h, p))) need_pos.push_back(p);
     };
     for (auto& c : B.work) {
         int32_t sp, ep;
@@ -1450,7 +1484,6 @@ static int32_t span_count_tiles(SpanBatch& B, const std::vector<int32_t>& need_p
         PISCES_HIP_CHECK(h, h->d_counts.reserve(PISCES_COUNTS_PER_LOCUS));
         if (window) PISCES_HIP_CHECK(h, h->d_sumq.reserve(PISCES_COUNTS_PER_LOCUS));
     }
-    B.d_folded = B.fold_ok ? h->d_folded.p : (const int32_t*)nullptr;
     return PISCES_OK;
 }
 
@@ -1494,7 +1527,7 @@ static int32_t span_count_rows(SpanBatch& B)
         PISCES_HIP_CHECK(h, h->d_rows.reserve(n_rows * PISCES_COUNTS_PER_LOCUS));
         { int32_t rcu = meta_upload(h, h->d_row_idx.p, need.data(), n_rows * sizeof(long long)); if (rcu) return rcu; }
         hipLaunchKernelGGL(gather_count_rows_kernel, dim3((unsigned)((n_rows * PISCES_COUNTS_PER_LOCUS + 255) / 256)), dim3(256), 0, h->stream,
-                           (const int32_t*)h->d_counts.p, B.d_folded, (const long long*)h->d_row_idx.p, (int32_t)n_rows, h->d_rows.p);
+                           (const int32_t*)h->d_counts.p, B.scope->fold.d_folded, (const long long*)h->d_row_idx.p, (int32_t)n_rows, h->d_rows.p);
         PISCES_HIP_CHECK(h, hipGetLastError());
         h->pcie[3] += (int64_t)(n_rows * PISCES_COUNTS_PER_LOCUS * sizeof(int32_t));
         PISCES_HIP_CHECK(h, hipMemcpyAsync(h->h_counts, h->d_rows.p, n_rows * PISCES_COUNTS_PER_LOCUS * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
@@ -1661,8 +1694,8 @@ static int32_t span_device_pass(SpanBatch& B, const std::vector<const HostCandid
         if (rcx) return rcx;
     }
     hipLaunchKernelGGL(call_spanning_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, h->stream, h->d_cands.p, n, h->d_counts.p,
-                       h->d_alleles.p, h->d_ref.p, h->ref_len, h->cfg.expect_stitched_reads, h->d_cand_records.p, h->d_cand_callable.p, h->P,
-                       window ? h->d_sumq.p : (const double*)nullptr, B.d_folded, wanted, h->exact_on ? (const int32_t*)h->d_exact_out.p : (const int32_t*)nullptr);
+                       h->d_alleles.p, h->d_ref.p, h->ref_len, h->cfg.expect_stitched_reads, h->d_cand_records.p, h->d_cand_callable.p,
+                       launch_params(h, B.scope->launch_values(h)), window ? h->d_sumq.p : (const double*)nullptr, B.scope->fold.d_folded, wanted, h->exact_on ? (const int32_t*)h->d_exact_out.p : (const int32_t*)nullptr);
     PISCES_HIP_CHECK(h, hipGetLastError());
     if (h->indel_repeat_threshold > 0 && wanted != kSpanningFlagsOnly) {   // FilterType.IndelRepeatLength, AlleleProcessor.cs:52-57: into the records in place, ahead of the copy-out
         hipLaunchKernelGGL(indel_repeat_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, h->stream, h->d_cands.p, n, h->d_alleles.p, h->d_ref.p, h->ref_len,
@@ -1840,7 +1873,7 @@ static void span_report(SpanBatch& B, std::vector<PiscesCalledAllele>& recs, std
         const bool forced = have_forced && is_forced_allele(h, c);
         const bool reportable = B.callable[i] && inside_intervals(h, c.position);
         if (B.callable[i] && owned(h, c.position)) (*n_called) += forced ? 2 : 1;
-        if (forced && !h->snv_walk && c.category == PISCES_CAT_SNV && reportable && !split_dirty_at(h, c.position)) {   // MNV calling off: the tile kernels report it,
+        if (forced && !h->snv_walk && c.category == PISCES_CAT_SNV && reportable && !B.scope->dirty_at(c.position)) {   // MNV calling off: the tile kernels report it,
             (*n_called)--;                                                                                         // and have counted it once
             continue;
         }
@@ -1868,9 +1901,9 @@ static void span_report(SpanBatch& B, std::vector<PiscesCalledAllele>& recs, std
 // this), and every callable allele is processed again.  ref_overrides: Reference alleles that reallocation added support to
 // (they replace the tile kernels' Reference record of that position).
 // blocks_first: the tile kernels of this flush are enqueued already (their Reference records do not know the reference support that
-// gapped MNVs of THIS batch take: the Reference alleles of those positions come from here, as overrides), and h->fold says where their
+// gapped MNVs of THIS batch take: the Reference alleles of those positions come from here, as overrides), and S.fold says where their
 // folded counts lie.  The stages follow the host profile's phases (prof[1..6]; prof[11]: the reallocator).
-static int32_t call_spanning(PiscesHip* h, const std::vector<int32_t>& keys, int32_t up_to_position, std::vector<PiscesCalledAllele>& recs,
+static int32_t call_spanning(PiscesHip* h, const FlushScope& S, const std::vector<int32_t>& keys, int32_t up_to_position, std::vector<PiscesCalledAllele>& recs,
                              std::vector<HostCandidate>& called, int64_t* n_called, int64_t* n_collapsed,
                              std::vector<PiscesCalledAllele>& ref_overrides, bool blocks_first = false)
 {
@@ -1883,6 +1916,7 @@ static int32_t call_spanning(PiscesHip* h, const std::vector<int32_t>& keys, int
     auto phase = [&](int i) { prof.reset(); prof.reset(new HostTimer(h->prof_on ? &h->prof[i] : nullptr)); };
     SpanBatch B;
     B.h = h;
+    B.scope = &S;
     B.keys = &keys;
     B.up_to_position = up_to_position;
     B.blocks_first = blocks_first;
@@ -2273,16 +2307,17 @@ static int32_t flush_build(PiscesHip* h, int32_t up_to_position, PiscesHip::Flus
     if (!final_flush && block_key(h, up_to_position) == h->last_up_to_block_key) return PISCES_OK;
     r.keys = select_flush_blocks(h, up_to_position, final_flush);
     const std::vector<int32_t>& keys = r.keys;
-    // MNV calling on, split form: the dirty loci of the batch, the SNV groups on them, the tile kernels' parameters for this flush
-    struct SplitGuard { PiscesHip* h; ~SplitGuard() { split_restore(h); } } split_guard{h};
-    { HostTimer prof_split(h->prof_on ? &h->prof[10] : nullptr); int32_t rcs = split_prepare(h, keys, final_flush ? -1 : up_to_position); if (rcs) return rcs; }
+    // what lives for this flush; MNV calling on, split form: the dirty loci of the batch, the SNV groups on them, refs_only of its launches
+    FlushScope S(h);
+    { HostTimer prof_split(h->prof_on ? &h->prof[10] : nullptr); int32_t rcs = split_prepare(h, S, keys, final_flush ? -1 : up_to_position); if (rcs) return rcs; }
     // The tile kernels first when they are the fused kernel over a run of whole blocks: their launch leaves the folded counts of every
     // locus for the candidate kernel (no second walk over the reads for point alleles, MNVs and deletions), and it runs while the host
     // collects the candidates.  Otherwise (counts in HBM, NoiseModel.Window, an interval set, an observation log) the candidates go first:
     // with MNV calling on they register the reference support that gapped MNVs take, which the tile kernels' Reference records must see
     // (AlleleCaller.cs:95, CoverageCalculator.cs:82-97).
     CallBlocksInFlight st;
-    const bool blocks_first = fused_regular_applies(h, keys);
+    S.path = plan_tile_path(h, keys);
+    const bool blocks_first = S.path.blocks_first;
     int32_t rc = PISCES_OK;
     if (blocks_first) {
         // (the folded counts only when a candidate can ask for them: 72 B a locus that an SNV-only flush need not write)
@@ -2290,19 +2325,19 @@ static int32_t flush_build(PiscesHip* h, int32_t up_to_position, PiscesHip::Flus
         if (!want_folded)
             for (auto& kv : h->blocks)
                 if (!kv.second.cands.empty() || !kv.second.unwalked.empty()) { want_folded = true; break; }
-        rc = call_blocks_enqueue(h, keys, true, -1, &st, want_folded);
+        rc = call_blocks_enqueue(h, S, keys, true, -1, &st, want_folded);
         if (rc) return rc;
     }
     std::vector<PiscesCalledAllele> span_recs, ref_overrides;
-    rc = call_spanning(h, keys, final_flush ? -1 : up_to_position, span_recs, r.cands, &r.called, &r.collapsed, ref_overrides, blocks_first && st.active);
-    h->fold.valid = false;
+    rc = call_spanning(h, S, keys, final_flush ? -1 : up_to_position, span_recs, r.cands, &r.called, &r.collapsed, ref_overrides, blocks_first && st.active);
     if (rc) return rc;
     std::unique_ptr<HostTimer> prof(new HostTimer(h->prof_on ? &h->prof[7] : nullptr));
     // per-locus genotypers: on the device, over the tile kernels' slots, when nothing joins their rows; else the host pass over the merged rows
     const bool device_genotyper = germline(h) && h->device_genotyper && span_recs.empty() && h->forced.empty() && ref_overrides.empty();
     const bool host_genotyper = germline(h) && !device_genotyper;
     if (!blocks_first) {
-        rc = call_blocks_enqueue(h, keys, true, -1, &st, false, device_genotyper);
+        S.path = plan_tile_path(h, keys);   // (again: the candidates may have registered reference support of gapped MNVs in these blocks — counts in HBM then)
+        rc = call_blocks_enqueue(h, S, keys, true, -1, &st, false, device_genotyper);
         if (rc) return rc;
     }
     if (st.active) {
@@ -2500,9 +2535,10 @@ int32_t pisces_hip_flush_begin(PiscesHip* h, int32_t up_to_position)
     // what the compacted log can hold at most: the entries that are not known holes
     const int64_t bound = std::max<int64_t>(0, h->log_ub - h->log_known_holes);
     CallBlocksInFlight st;
-    if (h->mnv_split) h->P.refs_only = 0;   // (no dirty locus in this batch: every SNV is the allele counts')
-    int32_t rc = call_blocks_enqueue(h, keys, true, bound, &st);
-    split_restore(h);
+    FlushScope S(h);
+    if (h->mnv_split) S.refs_only = 0;   // (no dirty locus in this batch: every SNV is the allele counts')
+    S.path = plan_tile_path(h, keys);
+    int32_t rc = call_blocks_enqueue(h, S, keys, true, bound, &st);
     if (rc) return rc;
     if (st.active) PISCES_HIP_CHECK(h, hipEventRecord(A.done, h->stream));
     if (!keys.empty()) h->host_time[3] += 1.0;

@@ -1126,7 +1126,8 @@ static int32_t add_decoded_reads_store(PiscesHip* h, int64_t found_slots, int64_
 }
 
 // the flush's kernel: reads of the store (+ the bucketed tuples of pisces_hip_add_observations) -> LDS histogram -> calls
-static hipError_t launch_call_store_tiles(PiscesHip* h, hipStream_t s, const uint32_t* d_tuples, const PiscesTile* d_tiles /* or nullptr: R */,
+// P: the parameters of this launch, by value to the kernel (launch_params, surface_flush.inc.h)
+static hipError_t launch_call_store_tiles(PiscesHip* h, hipStream_t s, const DeviceParams& P, const uint32_t* d_tuples, const PiscesTile* d_tiles /* or nullptr: R */,
                                           const RegularTiles& R, int32_t n_tiles, const uint8_t* d_ref, int32_t ref_start, int64_t ref_len, PiscesCalledAllele* d_records, PiscesTileResult* d_tr,
                                           hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr)
 {
@@ -1147,7 +1148,7 @@ static hipError_t launch_call_store_tiles(PiscesHip* h, hipStream_t s, const uin
     const int32_t walk_prio = (nw == 2 && (int64_t)n_tiles <= 8 * (int64_t)h->n_cus) ? 1 : 0;
 #define PISCES_LAUNCH_STORE(NW)                                                                                                                     \
     hipExtLaunchKernelGGL(call_store_tiles_kernel<NW>, dim3((unsigned)n_tiles), dim3(64 * NW), 0u, s, e0, e1, 0u, V, d_tuples, d_tiles, R, n_tiles, trade_cus, walk_prio, d_ref, \
-                          ref_start, ref_len, d_records, d_tr, h->P, (const DeviceParams*)h->d_params.p)
+                          ref_start, ref_len, d_records, d_tr, P, (const DeviceParams*)h->d_params.p)
     if (nw >= 16) PISCES_LAUNCH_STORE(16);
     else if (nw >= 8) PISCES_LAUNCH_STORE(8);
     else if (nw >= 4) PISCES_LAUNCH_STORE(4);

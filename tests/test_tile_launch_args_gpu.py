@@ -170,9 +170,10 @@ def test_a_graph_of_two_launches_equals_the_plain_launch(torch_cuda, form):
 def test_fields_that_change_between_the_flushes_of_a_streaming_run(torch_cuda, form):
     """Two 1000-locus blocks, a few hundred reads each, MNV calling on, through the observation log (the path on which a flush calls
     call_tiles_wave_kernel): refs_only and the dirty-locus bitmap of the second flush are not those of the first, and neither is what the
-    handle was created with.  (The folded-count window, the other per-flush part of DeviceParams, never reaches this kernel: it is set
-    around call_store_tiles_kernel only, and TileLaunchParams does not carry it.)  Rows, allele strings and TotalNumCalled against the
-    oracle's schedule."""
+    handle was created with.  Each flush carries its own in a FlushScope and hands them to the launch as TileLaunchParams; the handle's
+    parameters stay what pisces_hip_create made them.  (The folded-count window, the other part of a flush's scope, never reaches this
+    kernel: it goes to call_store_tiles_kernel's DeviceParams only, and TileLaunchParams cannot carry it.)  Rows, allele strings and
+    TotalNumCalled against the oracle's schedule."""
     from pisces_amd import engine
     from tests.test_gpu_parity import _mnv_reads, assert_records_match
     rng = np.random.default_rng(4711)
