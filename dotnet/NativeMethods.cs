@@ -76,6 +76,44 @@ namespace Pisces.Hip
     }
 
     [StructLayout(LayoutKind.Sequential)]
+    public struct PiscesVeadSite   // one variant site of a neighbourhood: its alleles lie in the call's allele bytes, ref then alt, at AlleleOffset
+    {
+        public int Position, RefLen, AltLen, AlleleOffset;
+    }
+
+    [StructLayout(LayoutKind.Sequential)]
+    public struct PiscesVeadNeighborhood   // [SiteBegin, SiteEnd) into the call's sites
+    {
+        public int SiteBegin, SiteEnd;
+    }
+
+    [StructLayout(LayoutKind.Sequential)]
+    public struct PiscesVeadOptions   // BamFilterParameters as far as VeadFinder reads them; pisces_hip_vead_default_options fills the defaults
+    {
+        public int MinBaseCallQuality, MinNumberVariantsInRead;
+    }
+
+    [StructLayout(LayoutKind.Sequential)]
+    public struct PiscesVeadGroup   // one VeadGroup: its neighbourhood, the batch index of its representative read, NumVeads, where its state bytes lie
+    {
+        public int Neighborhood, FirstRead, NVeads, Pad;
+        public long StateOffset;
+    }
+
+    [StructLayout(LayoutKind.Sequential)]
+    public struct PiscesVeadNeighborhoodInfo   // VcfNeighborhood.SetRangeOfInterest's four bounds and what the scan counted
+    {
+        public int First, LastWithLookAhead, SoftClipEndBefore, SoftClipPosAfter, NGroups, NClippedReads, NReadsUsed, GroupBegin;
+    }
+
+    [StructLayout(LayoutKind.Sequential)]
+    public struct PiscesVeadOut   // NOut points at three longs: groups, state bytes, 0
+    {
+        public IntPtr Groups, States, Info, NOut;
+        public long GroupCapacity, StateCapacity;
+    }
+
+    [StructLayout(LayoutKind.Sequential)]
     public struct PiscesHipConfig
     {
         public int AbiVersion, MinBaseCallQuality, NoiseLevel, MaxVariantQscore, MinVariantQscore, VariantQscoreFilter,
@@ -317,6 +355,13 @@ namespace Pisces.Hip
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pisces_hip_venn_consensus_device(IntPtr handle, ref PiscesVennOptions options, ref PiscesVennRows poolA, ref PiscesVennRows poolB, ref PiscesVennOut consensus, IntPtr stream);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pisces_hip_venn_consensus(ref PiscesVennOptions options, ref PiscesVennRows poolA, ref PiscesVennRows poolB, ref PiscesVennOut consensus);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pisces_hip_venn_combine(ref PiscesVennOptions options, IntPtr variantA, IntPtr variantB, int comparisonCase, out PiscesCalledAllele row, out PiscesConsensusInfo info, [Out] int[] vqAB);
+        // Scylla's read pass (INTEGRATION.md): HipVeadGroupSource calls the device entry once per chromosome for all its neighbourhoods, over the batch
+        // pisces_hip_bam_decode left on the device; the host entries serve a host without a device and single reads.
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pisces_hip_vead_default_options(out PiscesVeadOptions options);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pisces_hip_vead_site_states(ref PiscesVeadOptions options, int position, byte[] cigarOp, uint[] cigarLen, int nCigar, byte[] bases, byte[] quals, int nBases, [In] PiscesVeadSite[] sites, int nSites, byte[] alleles, long nAlleleBytes, [Out] byte[] states, out int nInRange);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pisces_hip_vead_neighborhood_info([In] PiscesVeadSite[] sites, int nSites, out PiscesVeadNeighborhoodInfo info);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pisces_hip_vead_groups(ref PiscesVeadOptions options, ref PiscesReadBatch batch, [In] PiscesVeadSite[] sites, int nSites, byte[] alleles, long nAlleleBytes, [In] PiscesVeadNeighborhood[] neighborhoods, int nNeighborhoods, ref PiscesVeadOut groups);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pisces_hip_vead_groups_device(IntPtr handle, ref PiscesVeadOptions options, IntPtr deviceBatch, long nCigarOps, long nBases, [In] PiscesVeadSite[] sites, int nSites, byte[] alleles, long nAlleleBytes, [In] PiscesVeadNeighborhood[] neighborhoods, int nNeighborhoods, ref PiscesVeadOut groups, IntPtr stream);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pisces_hip_get_spanning_read_counts(IntPtr handle, int preceding, int trailing, int isInsertion, [Out] int[] counts);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pisces_hip_exact_span_direction(int cs, int ce, byte[] cigarOp, uint[] cigarLen, int nCigar, byte[] dirRunType, uint[] dirRunLen, int nRuns, int preceding, int trailing, int isInsertion);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pisces_hip_vcf_default_config(out PiscesVcfConfig cfg);

@@ -1104,6 +1104,69 @@ int32_t pisces_hip_venn_consensus(const PiscesVennOptions* opts, const PiscesVen
 int32_t pisces_hip_venn_combine(const PiscesVennOptions* opts, const PiscesCalledAllele* a, const PiscesCalledAllele* b, int32_t comparison_case,
                                 PiscesCalledAllele* row_out, PiscesConsensusInfo* info_out, int32_t* vq_ab);
 
+/* ---- Scylla's read pass (src/lib/VariantPhasing): vead groups per neighbourhood from resident reads ----------------------------------
+ * For every neighbourhood of nearby variant sites Scylla asks each read, site by site, whether it carries the variant, the reference,
+ * something else or nothing usable (a "vead", VeadFinder.FindVariantResults) and collapses identical answers into counted groups
+ * (VeadGroupSource.GetVeadGroups).  csrc/vead.h restates the decision for host and device; the reference's quirks are kept (N, =, X, H
+ * and P operations advance nothing in the walk; a "gone past" result is overwritten by the tail below the loop).
+ * A site's state is one byte.  A site whose own alleles are one equal base (A>A) prints the same for REF and ALT in the reference's group
+ * key (Vead.ToVariantSequence): it is given as PISCES_VEAD_REF, so equal keys are equal state vectors. */
+#define PISCES_VEAD_NONE  0   /* N>N: out of range, insufficient data, unknown */
+#define PISCES_VEAD_REF   1   /* ref[0]>ref[0] */
+#define PISCES_VEAD_ALT   2   /* ref>alt */
+#define PISCES_VEAD_OTHER 3   /* X>X */
+#define PISCES_VEAD_MAX_SITES 256   /* sites of one neighbourhood (the reference has no cap; neighbourhoods chain at PhasingDistance 50) */
+typedef struct PiscesVeadSite { int32_t position, ref_len, alt_len; int32_t allele_offset; } PiscesVeadSite; /* ref bytes then alt bytes in `alleles` */
+typedef struct PiscesVeadNeighborhood { int32_t site_begin, site_end; } PiscesVeadNeighborhood;           /* [begin, end) into sites */
+typedef struct PiscesVeadOptions { int32_t min_base_call_quality /* 20 */, min_number_variants_in_read /* 1 */; } PiscesVeadOptions;
+typedef struct PiscesVeadGroup { int32_t neighborhood, first_read, n_veads; int32_t pad; int64_t state_offset; } PiscesVeadGroup;
+typedef struct PiscesVeadNeighborhoodInfo { int32_t first, last_with_look_ahead, soft_clip_end_before, soft_clip_pos_after;
+                                            int32_t n_groups, n_clipped_reads, n_reads_used, group_begin; } PiscesVeadNeighborhoodInfo;
+/* Where the groups go.  Host memory for pisces_hip_vead_groups, device-accessible for pisces_hip_vead_groups_device.  info[n_neighbourhoods]
+ * is sized by the input and always written; n_out[3] = {groups, state bytes, 0}.  When a count is above its capacity only n_out and info
+ * are written: repeat with larger arrays. */
+typedef struct PiscesVeadOut {
+    PiscesVeadGroup* groups;
+    uint8_t* states;                     /* one byte a site of the group's neighbourhood at groups[g].state_offset */
+    PiscesVeadNeighborhoodInfo* info;
+    int64_t* n_out;
+    int64_t group_capacity, state_capacity;
+} PiscesVeadOut;
+int32_t pisces_hip_vead_default_options(PiscesVeadOptions* opts);
+/* ONE read against one site list, host only, no handle: states[n_sites] and *n_in_range (numSitesFoundInRead; the read is a vead when it
+ * reaches min_number_variants_in_read).  position is Read.Position (1-based).  Returns PISCES_OK or PISCES_E_INVALID_ARG. */
+int32_t pisces_hip_vead_site_states(const PiscesVeadOptions* opts, int32_t position, const uint8_t* cigar_op, const uint32_t* cigar_len, int32_t n_cigar,
+                                    const uint8_t* bases, const uint8_t* quals, int32_t n_bases, const PiscesVeadSite* sites, int32_t n_sites,
+                                    const uint8_t* alleles, int64_t n_allele_bytes, uint8_t* states, int32_t* n_in_range);
+/* VcfNeighborhood.SetRangeOfInterest for a site list in the caller's order (nothing is sorted), host only: the four bounds of *info. */
+int32_t pisces_hip_vead_neighborhood_info(const PiscesVeadSite* sites, int32_t n_sites, PiscesVeadNeighborhoodInfo* info);
+/* The groups of every neighbourhood over a HOST batch: the statement of the output contract and the function the device runs.
+ * Neighbourhoods come in input order; within one the groups come in the order of their first read (the reference's Dictionary enumerates
+ * in insertion order); first_read is the batch index of the representative vead (the host makes VeadGroup.Name from it), n_veads the
+ * group's count.  Per neighbourhood the scan is VeadGroupSource's: every read up to and including the first with position >
+ * last_with_look_ahead is tested for IsClippedWithinNeighborhood (n_clipped_reads, counted BEFORE the skip test), a read with EndPosition <
+ * first is skipped, the others are used (n_reads_used) and are veads when enough sites are in range.  The MAPQ, duplicate and proper-pair
+ * tests belong to whoever made the batch.  Refused, each with a message: positions that descend (PISCES_E_INVALID_ARG naming the first
+ * offending read, n_out = {PISCES_E_INVALID_ARG, 0, that read}: sortedness is what makes "stop at the first read past" a per-read test),
+ * more than PISCES_VEAD_MAX_SITES sites in a neighbourhood (PISCES_E_UNSUPPORTED), an empty neighbourhood or one outside the site list, a
+ * site with ref_len or alt_len below 1 or allele bytes outside `alleles`, null arrays, negative sizes (PISCES_E_INVALID_ARG);
+ * PISCES_E_BUFFER_TOO_SMALL with the counts in n_out when a capacity is short.  Bit-reproducible from run to run. */
+int32_t pisces_hip_vead_groups(const PiscesVeadOptions* opts, const PiscesReadBatch* batch, const PiscesVeadSite* sites, int32_t n_sites,
+                               const uint8_t* alleles, int64_t n_allele_bytes, const PiscesVeadNeighborhood* neighbourhoods, int32_t n_neighbourhoods,
+                               const PiscesVeadOut* out);
+/* The same over reads in device memory: device_batch as for pisces_hip_add_device_reads (n_cigar_ops, n_bases: its array sizes), or NULL
+ * for the handle's decoded batch (pisces_hip_bam_decode) before it has moved into the store.  sites, alleles and neighbourhoods are small
+ * host arrays; the library uploads them.  Every array of `out` is caller-owned device-accessible memory.  The call waits ONCE, for the
+ * read range of every neighbourhood and the sortedness verdict (8 bytes a neighbourhood come back): that sizes the scratch and lets
+ * descending positions be refused with a status and a message as above.  Everything behind that is enqueued on `stream` (NULL: the
+ * handle's own) and the call returns without waiting for it; a count above its capacity leaves only n_out and info written.  The
+ * output is the host entry's, byte for byte, whichever wave runs first.  The handle's reads, store and decoded batch are left alone.
+ * Deviation: the reference hands Scylla every BAM record (BamFileAlignmentExtractor.GetNextAlignment); the decode drops unmapped,
+ * secondary and CIGAR-less records (AlignmentSource.ShouldSkipRead).  A host that wants those phased passes its own batch. */
+int32_t pisces_hip_vead_groups_device(PiscesHip* h, const PiscesVeadOptions* opts, const PiscesReadBatch* device_batch, int64_t n_cigar_ops, int64_t n_bases,
+                                      const PiscesVeadSite* sites, int32_t n_sites, const uint8_t* alleles, int64_t n_allele_bytes,
+                                      const PiscesVeadNeighborhood* neighbourhoods, int32_t n_neighbourhoods, const PiscesVeadOut* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

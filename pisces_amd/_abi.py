@@ -173,6 +173,42 @@ class PiscesVennOut(C.Structure):
                 ("allele_capacity", C.c_int64)]
 
 
+# Scylla's read pass (pisces_hip_vead_*)
+class PiscesVeadSite(C.Structure):
+    _fields_ = [("position", C.c_int32), ("ref_len", C.c_int32), ("alt_len", C.c_int32), ("allele_offset", C.c_int32)]
+
+
+class PiscesVeadNeighborhood(C.Structure):
+    _fields_ = [("site_begin", C.c_int32), ("site_end", C.c_int32)]
+
+
+class PiscesVeadOptions(C.Structure):
+    _fields_ = [("min_base_call_quality", C.c_int32), ("min_number_variants_in_read", C.c_int32)]
+
+
+class PiscesVeadGroup(C.Structure):
+    _fields_ = [("neighborhood", C.c_int32), ("first_read", C.c_int32), ("n_veads", C.c_int32), ("pad", C.c_int32), ("state_offset", C.c_int64)]
+
+
+class PiscesVeadNeighborhoodInfo(C.Structure):
+    _fields_ = [("first", C.c_int32), ("last_with_look_ahead", C.c_int32), ("soft_clip_end_before", C.c_int32), ("soft_clip_pos_after", C.c_int32),
+                ("n_groups", C.c_int32), ("n_clipped_reads", C.c_int32), ("n_reads_used", C.c_int32), ("group_begin", C.c_int32)]
+
+
+class PiscesVeadOut(C.Structure):
+    _fields_ = [("groups", C.c_void_p), ("states", C.c_void_p), ("info", C.c_void_p), ("n_out", C.c_void_p), ("group_capacity", C.c_int64),
+                ("state_capacity", C.c_int64)]
+
+
+VEAD_NONE, VEAD_REF, VEAD_ALT, VEAD_OTHER = 0, 1, 2, 3
+VEAD_MAX_SITES = 256
+VEAD_SITE_DTYPE = np.dtype([("position", "<i4"), ("ref_len", "<i4"), ("alt_len", "<i4"), ("allele_offset", "<i4")])
+VEAD_NEIGHBORHOOD_DTYPE = np.dtype([("site_begin", "<i4"), ("site_end", "<i4")])
+VEAD_GROUP_DTYPE = np.dtype([("neighborhood", "<i4"), ("first_read", "<i4"), ("n_veads", "<i4"), ("pad", "<i4"), ("state_offset", "<i8")])
+VEAD_INFO_DTYPE = np.dtype([("first", "<i4"), ("last_with_look_ahead", "<i4"), ("soft_clip_end_before", "<i4"), ("soft_clip_pos_after", "<i4"),
+                            ("n_groups", "<i4"), ("n_clipped_reads", "<i4"), ("n_reads_used", "<i4"), ("group_begin", "<i4")])
+
+
 # VariantComparisonCase (src/exe/VennVcf/VennVcf.cs:15-21) and the Venn classes of an input row (WriteVarsToVennFiles)
 VENN_AGREED_ON_REFERENCE, VENN_AGREED_ON_ALTERNATE, VENN_ONE_REFERENCE_ONE_ALTERNATE, VENN_CAN_NOT_COMBINE = 0, 1, 2, 3
 VENN_NONE, VENN_AND, VENN_NOT = 0, 1, 2

@@ -33,6 +33,7 @@ EXPORTS = [
     "pisces_hip_indel_repeat_length", "pisces_hip_set_indel_repeat_filter",
     "pisces_hip_vqr_default_options", "pisces_hip_vqr_count_device", "pisces_hip_vqr_count", "pisces_hip_vqr_tables", "pisces_hip_vqr_apply_device",
     "pisces_hip_venn_default_options", "pisces_hip_venn_consensus_device", "pisces_hip_venn_consensus", "pisces_hip_venn_combine",
+    "pisces_hip_vead_default_options", "pisces_hip_vead_site_states", "pisces_hip_vead_neighborhood_info", "pisces_hip_vead_groups", "pisces_hip_vead_groups_device",
 ]
 
 
@@ -179,6 +180,11 @@ def _load():
         "pisces_hip_venn_consensus_device": (i32, [vp, P(_abi.PiscesVennOptions), P(_abi.PiscesVennRows), P(_abi.PiscesVennRows), P(_abi.PiscesVennOut), vp]),
         "pisces_hip_venn_consensus": (i32, [P(_abi.PiscesVennOptions), P(_abi.PiscesVennRows), P(_abi.PiscesVennRows), P(_abi.PiscesVennOut)]),
         "pisces_hip_venn_combine": (i32, [P(_abi.PiscesVennOptions), vp, vp, i32, vp, P(_abi.PiscesConsensusInfo), vp]),
+        "pisces_hip_vead_default_options": (i32, [P(_abi.PiscesVeadOptions)]),
+        "pisces_hip_vead_site_states": (i32, [P(_abi.PiscesVeadOptions), i32, vp, vp, i32, vp, vp, i32, vp, i32, vp, i64, vp, P(i32)]),
+        "pisces_hip_vead_neighborhood_info": (i32, [vp, i32, P(_abi.PiscesVeadNeighborhoodInfo)]),
+        "pisces_hip_vead_groups": (i32, [P(_abi.PiscesVeadOptions), P(_abi.PiscesReadBatch), vp, i32, vp, i64, vp, i32, P(_abi.PiscesVeadOut)]),
+        "pisces_hip_vead_groups_device": (i32, [vp, P(_abi.PiscesVeadOptions), P(_abi.PiscesReadBatch), i64, i64, vp, i32, vp, i64, vp, i32, P(_abi.PiscesVeadOut), vp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(lib, name)   # AttributeError here = a declared symbol is not exported

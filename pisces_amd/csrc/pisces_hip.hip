@@ -44,6 +44,7 @@
 #include "vcf_kernels.hip.h"
 #include "vqr_kernels.hip.h"
 #include "venn_kernels.hip.h"
+#include "vead_kernels.hip.h"
 #include "vcf_format.h"
 
 using namespace pisces;
@@ -641,6 +642,18 @@ public:
     DeviceBuf<uint32_t> d_venn_prefix;
     DeviceBuf<int64_t> d_venn_chunk;
     DeviceBuf<unsigned long long> d_venn_ctrl;
+    // pisces_hip_vead_groups_device (vead_kernels.hip.h, Args): the uploaded neighbourhoods, per-read spans, the (neighbourhood, read) pairs' scratch
+    struct VeadScratch {
+        DeviceBuf<PiscesVeadSite> sites;
+        DeviceBuf<uint8_t> alleles, clip, is_vead;
+        DeviceBuf<PiscesVeadNeighborhood> nbhd;
+        DeviceBuf<vead::Bounds> bounds;
+        DeviceBuf<veaddev::Plan> plan;
+        DeviceBuf<int2> work;
+        DeviceBuf<int32_t> end, range, counts, table, slot_count, pair_count, work_groups;
+        DeviceBuf<unsigned long long> ctrl, keys;
+        DeviceBuf<int64_t> prefix;
+    } vead;
 };
 
 #define PISCES_HIP_CHECK(h, expr)                                                              \
@@ -1251,6 +1264,7 @@ int32_t pisces_hip_set_owned_range(PiscesHip* h, int32_t lo, int32_t hi)
 #include "surface_vqr.inc.h"
 
 #include "surface_venn.inc.h"
+#include "surface_vead.inc.h"
 
 int32_t pisces_hip_synchronize(PiscesHip* h)
 {

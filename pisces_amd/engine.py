@@ -660,6 +660,20 @@ class HipVariantCaller:
         opts = options if options is not None else venn_options()
         _check(self._h, lib.pisces_hip_venn_consensus_device(self._h, C.byref(opts), C.byref(rows_a), C.byref(rows_b), C.byref(out), self._stream_arg(stream)))
 
+    def vead_groups_device(self, sites, neighborhoods, out, batch=None, options=None, stream=None):
+        """pisces_hip_vead_groups_device: Scylla's read pass over reads in device memory.  sites: vead_sites([(position, ref, alt), ...]);
+        neighborhoods: [(site_begin, site_end), ...] into them; batch: a DeviceReadBatch, or None for the batch bam_decode left on the
+        device; out: vead_out(...) over torch tensors or raw device addresses, whose n_out is a device-accessible int64[3] that receives
+        groups, state bytes and 0 (only n_out and info are written when a count is above its capacity).  The call waits once for the
+        neighbourhoods' read ranges, everything behind that is asynchronous on `stream` (None = the handle's own)."""
+        opts = options if options is not None else vead_options()
+        site_rows, alleles = sites
+        nb = _vead_neighborhoods(neighborhoods)
+        _check(self._h, lib.pisces_hip_vead_groups_device(self._h, C.byref(opts), C.byref(batch.c) if batch is not None else None,
+                                                          batch.n_ops if batch is not None else 0, batch.n_bases if batch is not None else 0,
+                                                          site_rows.ctypes.data, len(site_rows), alleles.ctypes.data, alleles.size, nb.ctypes.data, len(nb),
+                                                          C.byref(out), self._stream_arg(stream)))
+
     def accumulate_tiles(self, d_tuples, d_tiles, n_tiles, d_counts, stream=None):
         _check(self._h, lib.pisces_hip_accumulate_tiles(self._h, d_tuples, d_tiles, n_tiles, d_counts, self._stream_arg(stream)))
 
@@ -1242,3 +1256,104 @@ def find_candidates(batch, ref, min_base_call_quality=20, snvs_and_mnvs=True, ca
         if n < 0:
             raise PiscesHipError(int(n), "find_candidates failed")
         return _candidate_dicts(cands, pool, n)
+
+
+# ---- Scylla's read pass (pisces_hip_vead_*) ---------------------------------------------------------------------------------------------
+def vead_options(**overrides):
+    """PiscesVeadOptions with Scylla's defaults (pisces_hip_vead_default_options), fields overridden by name."""
+    opts = _abi.PiscesVeadOptions()
+    _check(None, lib.pisces_hip_vead_default_options(C.byref(opts)))
+    for k, v in overrides.items():
+        if not hasattr(opts, k):
+            raise AttributeError(f"PiscesVeadOptions has no field {k!r}")
+        setattr(opts, k, v)
+    return opts
+
+
+def vead_sites(sites):
+    """[(position, ref, alt), ...] (alleles as bytes or str) as (VEAD_SITE_DTYPE rows, the allele bytes they point into).  A pair that
+    vead_sites made is passed through."""
+    if isinstance(sites, tuple) and len(sites) == 2 and getattr(sites[0], "dtype", None) == _abi.VEAD_SITE_DTYPE:
+        return sites
+    rows = np.zeros(len(sites), dtype=_abi.VEAD_SITE_DTYPE)
+    pool = bytearray()
+    for i, (position, ref, alt) in enumerate(sites):
+        ref = ref.encode() if isinstance(ref, str) else bytes(ref)
+        alt = alt.encode() if isinstance(alt, str) else bytes(alt)
+        rows[i] = (position, len(ref), len(alt), len(pool))
+        pool += ref + alt
+    alleles = np.frombuffer(bytes(pool) + b"\0", dtype=np.uint8).copy()[:len(pool)]
+    return rows, alleles
+
+
+def _vead_neighborhoods(neighborhoods):
+    nb = np.zeros(len(neighborhoods), dtype=_abi.VEAD_NEIGHBORHOOD_DTYPE)
+    for i, (b, e) in enumerate(neighborhoods):
+        nb[i] = (b, e)
+    return nb
+
+
+def vead_out(groups, states, info, n_out, group_capacity, state_capacity):
+    """PiscesVeadOut: where the groups go (torch tensors, numpy arrays, ctypes arrays or raw addresses; the caller keeps them alive)."""
+    o = _abi.PiscesVeadOut()
+    o.groups, o.states, o.info, o.n_out = _address(groups), _address(states), _address(info), _address(n_out)
+    o.group_capacity, o.state_capacity = int(group_capacity), int(state_capacity)
+    return o
+
+
+def vead_site_states(position, cigar, bases, quals, sites, options=None):
+    """pisces_hip_vead_site_states: what ONE read (Read.Position 1-based, cigar [(op char, length), ...], bases, quals) says about each of
+    `sites` (vead_sites input).  Returns (states uint8[n_sites], sites in range)."""
+    opts = options if options is not None else vead_options()
+    rows, alleles = vead_sites(sites)
+    ops = np.array([ord(o) if isinstance(o, str) else int(o) for o, _ in cigar], dtype=np.uint8)
+    lens = np.array([int(n) for _, n in cigar], dtype=np.uint32)
+    b = np.frombuffer(bases.encode() if isinstance(bases, str) else bytes(bases), dtype=np.uint8)
+    q = np.ascontiguousarray(quals, dtype=np.uint8)
+    states = np.zeros(max(len(rows), 1), dtype=np.uint8)
+    found = C.c_int32(0)
+    _check(None, lib.pisces_hip_vead_site_states(C.byref(opts), int(position), ops.ctypes.data, lens.ctypes.data, len(ops), b.ctypes.data, q.ctypes.data,
+                                                 len(b), rows.ctypes.data, len(rows), alleles.ctypes.data, alleles.size, states.ctypes.data, C.byref(found)))
+    return states[:len(rows)], int(found.value)
+
+
+def vead_neighborhood_info(sites):
+    """pisces_hip_vead_neighborhood_info: (first, last_with_look_ahead, soft_clip_end_before, soft_clip_pos_after) of a site list in the
+    caller's order."""
+    rows, _ = vead_sites(sites)
+    info = _abi.PiscesVeadNeighborhoodInfo()
+    _check(None, lib.pisces_hip_vead_neighborhood_info(rows.ctypes.data, len(rows), C.byref(info)))
+    return info.first, info.last_with_look_ahead, info.soft_clip_end_before, info.soft_clip_pos_after
+
+
+def vead_groups(batch, sites, neighborhoods, options=None, capacities=None):
+    """pisces_hip_vead_groups: the vead groups of every neighbourhood over a HOST batch (a mapping or an object with the PiscesReadBatch
+    field names as numpy arrays).  Returns {groups (VEAD_GROUP_DTYPE), states (uint8), info (VEAD_INFO_DTYPE), n_out}.  capacities: (groups, state
+    bytes); by default the call is repeated with the sizes it reports."""
+    opts = options if options is not None else vead_options()
+    rows, alleles = vead_sites(sites)
+    nb = _vead_neighborhoods(neighborhoods)
+    get = (lambda k: batch[k]) if hasattr(batch, "__getitem__") else (lambda k: getattr(batch, k))
+    arrays = {k: np.ascontiguousarray(get(k), dtype=dt) for k, dt in (("position", np.int32), ("cigar_offset", np.int32), ("cigar_op", np.uint8),
+                                                                      ("cigar_len", np.uint32), ("seq_offset", np.int32), ("bases", np.uint8), ("quals", np.uint8))}
+    c = _abi.PiscesReadBatch()
+    c.n_reads = len(arrays["position"])
+    for k, a in arrays.items():
+        setattr(c, k, C.cast(C.c_void_p(a.ctypes.data if a.size else (np.zeros(1, a.dtype)).ctypes.data), type(getattr(c, k))))
+    caps = capacities if capacities is not None else (0, 0)
+    while True:
+        groups = np.zeros(max(caps[0], 1), dtype=_abi.VEAD_GROUP_DTYPE)
+        states = np.zeros(max(caps[1], 1), dtype=np.uint8)
+        info = np.zeros(max(len(nb), 1), dtype=_abi.VEAD_INFO_DTYPE)
+        n_out = np.zeros(3, dtype=np.int64)
+        out = vead_out(groups, states, info, n_out, caps[0], caps[1])
+        rc = lib.pisces_hip_vead_groups(C.byref(opts), C.byref(c), rows.ctypes.data, len(rows), alleles.ctypes.data, alleles.size, nb.ctypes.data, len(nb),
+                                        C.byref(out))
+        if rc == _abi.E_BUFFER_TOO_SMALL and capacities is None:
+            caps = (int(n_out[0]), int(n_out[1]))
+            continue
+        if rc != 0:
+            err = PiscesHipError(rc, (lib.pisces_hip_last_error(None) or b"").decode())
+            err.n_out = tuple(int(v) for v in n_out)
+            raise err
+        return {"groups": groups[:int(n_out[0])], "states": states[:int(n_out[1])], "info": info[:len(nb)], "n_out": tuple(int(v) for v in n_out)}
