@@ -114,6 +114,27 @@ namespace Pisces.Hip
     }
 
     [StructLayout(LayoutKind.Sequential)]
+    public struct PiscesNbhdCriteria   // PhasableVariantCriteria as far as NeighborhoodBuilder reads it; pisces_hip_nbhd_default_criteria fills the defaults
+    {
+        public int PhasingDistance, PassingVariantsOnly, HetVariantsOnly, MinPassingVariantsInNbhd;
+        public int Reserved0, Reserved1, Reserved2, Reserved3;
+    }
+
+    [StructLayout(LayoutKind.Sequential)]
+    public struct PiscesNbhdInfo   // one kept neighbourhood: its number among all, its two counts, SetRangeOfInterest's bounds, where its reference bytes lie
+    {
+        public int RawIndex, NPassing, NNonPassing, First, LastInVcf, LastWithLookAhead, SoftClipEndBefore, SoftClipPosAfter, RefLen, Reserved;
+        public long RefOffset;
+    }
+
+    [StructLayout(LayoutKind.Sequential)]
+    public struct PiscesNbhdOut   // NOut points at six longs: kept neighbourhoods, sites, allele bytes, reference bytes, raw neighbourhoods, eligible rows
+    {
+        public IntPtr Sites, Alleles, SiteRow, SiteOriginal, Neighbourhoods, Info, RefBytes, RowClass, NOut;
+        public long NbhdCapacity, SiteCapacity, AlleleCapacity, RefCapacity;
+    }
+
+    [StructLayout(LayoutKind.Sequential)]
     public struct PiscesHipConfig
     {
         public int AbiVersion, MinBaseCallQuality, NoiseLevel, MaxVariantQscore, MinVariantQscore, VariantQscoreFilter,
@@ -362,6 +383,11 @@ namespace Pisces.Hip
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pisces_hip_vead_neighborhood_info([In] PiscesVeadSite[] sites, int nSites, out PiscesVeadNeighborhoodInfo info);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pisces_hip_vead_groups(ref PiscesVeadOptions options, ref PiscesReadBatch batch, [In] PiscesVeadSite[] sites, int nSites, byte[] alleles, long nAlleleBytes, [In] PiscesVeadNeighborhood[] neighborhoods, int nNeighborhoods, ref PiscesVeadOut groups);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pisces_hip_vead_groups_device(IntPtr handle, ref PiscesVeadOptions options, IntPtr deviceBatch, long nCigarOps, long nBases, [In] PiscesVeadSite[] sites, int nSites, byte[] alleles, long nAlleleBytes, [In] PiscesVeadNeighborhood[] neighborhoods, int nNeighborhoods, ref PiscesVeadOut groups, IntPtr stream);
+
+        // Scylla's neighbourhoods (INTEGRATION.md): HipNeighborhoodBuilder calls the device entry once per chromosome over the rows a flush left on the device
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pisces_hip_nbhd_default_criteria(out PiscesNbhdCriteria criteria);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pisces_hip_nbhd_build(ref PiscesNbhdCriteria criteria, ref PiscesVennRows rows, byte[] reference, long referenceLength, ref PiscesNbhdOut tables);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pisces_hip_nbhd_build_device(IntPtr handle, ref PiscesNbhdCriteria criteria, ref PiscesVennRows rows, ref PiscesNbhdOut tables, IntPtr stream);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pisces_hip_get_spanning_read_counts(IntPtr handle, int preceding, int trailing, int isInsertion, [Out] int[] counts);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pisces_hip_exact_span_direction(int cs, int ce, byte[] cigarOp, uint[] cigarLen, int nCigar, byte[] dirRunType, uint[] dirRunLen, int nRuns, int preceding, int trailing, int isInsertion);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int pisces_hip_vcf_default_config(out PiscesVcfConfig cfg);

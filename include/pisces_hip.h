@@ -1167,6 +1167,82 @@ int32_t pisces_hip_vead_groups_device(PiscesHip* h, const PiscesVeadOptions* opt
                                       const PiscesVeadSite* sites, int32_t n_sites, const uint8_t* alleles, int64_t n_allele_bytes,
                                       const PiscesVeadNeighborhood* neighbourhoods, int32_t n_neighbourhoods, const PiscesVeadOut* out, void* stream);
 
+/* ---- Scylla's neighbourhoods (src/lib/VariantPhasing): the tables the read pass takes, from called rows ---------------------------------
+ * NeighborhoodBuilder, VariantSite, VcfNeighborhood and the front of CallableNeighborhood over the rows of ONE chromosome as a flush gives
+ * them out (PiscesVennRows; a row's alleles are its candidate's bytes when cand_index[r] >= 0, otherwise the single bases of
+ * PISCES_INFO_REF / PISCES_INFO_ALT).  csrc/nbhd.h restates the decision for host and device and quotes the C#:
+ *   - a row with PISCES_FILTER_FORCED_REPORT is skipped before anything else;
+ *   - a row is eligible unless it is a Reference row, of a category above PISCES_CAT_REFERENCE, one of the four no-calls of
+ *     CalledAllele.IsNocall (ALT12_LIKE_NOCALL, ALT_LIKE_NOCALL, HEMI_NOCALL, REF_LIKE_NOCALL; REF_AND_NOCALL and ALT_AND_NOCALL are not),
+ *     HOM_ALT with het_variants_only, or carries a filter (bits 0..13 of filter_bits; 14..15 are the phase set) with passing_variants_only;
+ *   - an eligible row is proximal when position - (position of the last ELIGIBLE row) < phasing_distance, strictly;
+ *   - the neighbourhoods are the maximal runs of two or more consecutive eligible rows each proximal to the one before; a distance below 1
+ *     gives none;
+ *   - a neighbourhood with passing < min_passing_variants_in_nbhd && non_passing > 0 is dropped and still takes a raw_index;
+ *   - the sites of a neighbourhood are sorted by position + (ref_len != alt_len), STABLY (within one position the equal-length alleles go
+ *     in front of the indels); the reference writes OriginalAlleleFromVcf back in the pre-sort order, so site s holds the alleles of row
+ *     site_row[s] and the original allele of row site_original[s];
+ *   - the bounds are pisces_hip_vead_neighborhood_info of the sorted sites, plus last_in_vcf.
+ * Deviations: .NET's List.Sort is unspecified among equal keys above 16 elements, the stable order is given at every
+ * size; the reference's split of one crushed multi-allelic VCF line at a full batch is not reproduced (rows are uncrushed). */
+typedef struct PiscesNbhdCriteria {
+    int32_t phasing_distance;              /* PhasableVariantCriteria.PhasingDistance, 50 */
+    int32_t passing_variants_only;         /* PassingVariantsOnly, 1 */
+    int32_t het_variants_only;             /* HetVariantsOnly, 0 */
+    int32_t min_passing_variants_in_nbhd;  /* MinPassingVariantsInNbhd, 0 */
+    int32_t reserved[4];
+} PiscesNbhdCriteria;
+/* one kept neighbourhood (48 bytes) */
+typedef struct PiscesNbhdInfo {
+    int32_t raw_index;                     /* its number among all neighbourhoods, dropped ones included (NbhdNum of one unbounded batch) */
+    int32_t n_passing, n_non_passing;      /* VcfNeighborhood.PassingVariants / NonPassingVariants */
+    int32_t first, last_in_vcf, last_with_look_ahead, soft_clip_end_before, soft_clip_pos_after;
+    int32_t ref_len;                       /* last_with_look_ahead - first bytes of NbhdReferenceSequenceSubstring ... */
+    int32_t reserved;
+    int64_t ref_offset;                    /* ... at this offset of ref_bytes */
+} PiscesNbhdInfo;
+#define PISCES_NBHD_ROW_FORCED     0   /* forced-report row, skipped */
+#define PISCES_NBHD_ROW_INELIGIBLE 1
+#define PISCES_NBHD_ROW_LONE       2   /* eligible, in no neighbourhood */
+#define PISCES_NBHD_ROW_DROPPED    3   /* in a dropped neighbourhood */
+#define PISCES_NBHD_ROW_KEPT       4   /* in a kept neighbourhood: a row phasing may replace */
+/* Where the tables go: host memory for pisces_hip_nbhd_build, device-accessible memory (pinned host memory included) for
+ * pisces_hip_nbhd_build_device.  sites / alleles / neighbourhoods are exactly what pisces_hip_vead_groups[_device] takes: the kept
+ * neighbourhoods in input order as [begin, end) into sites, each site's ref bytes then alt bytes starting where the previous site's end.
+ * n_out[6] = {kept neighbourhoods, sites, allele bytes, reference bytes, raw neighbourhoods, eligible rows}.  When one of the first four is
+ * above its capacity only n_out is written: repeat with larger arrays.  Rows that descend by position leave n_out = {PISCES_E_INVALID_ARG,
+ * 0, lowest offending row, 0, 0, 0}; otherwise an insertion, deletion or MNV row without a candidate to take bytes from leaves
+ * {PISCES_E_INVALID_ARG, 1, lowest such row, 0, 0, 0}; more than 2^31 - 1 allele or reference bytes {PISCES_E_UNSUPPORTED, 0, ...}.
+ * Nothing else is written then.  There is no cap on the sites of a neighbourhood (PISCES_VEAD_MAX_SITES is the read pass's, which
+ * refuses it). */
+typedef struct PiscesNbhdOut {
+    PiscesVeadSite* sites;                 /* site_capacity */
+    uint8_t* alleles;                      /* allele_capacity bytes */
+    int32_t* site_row;                     /* site_capacity: the row whose alleles site s holds */
+    int32_t* site_original;                /* site_capacity: the row of the s-th site before sorting (OriginalAlleleFromVcf) */
+    PiscesVeadNeighborhood* neighbourhoods;/* nbhd_capacity */
+    PiscesNbhdInfo* info;                  /* nbhd_capacity */
+    uint8_t* ref_bytes;                    /* ref_capacity */
+    uint8_t* row_class;                    /* optional, one PISCES_NBHD_ROW_* a row of the input (rows->n of them; min(n, *count) are written) */
+    int64_t* n_out;                        /* [6] */
+    int64_t nbhd_capacity, site_capacity, allele_capacity, ref_capacity;
+} PiscesNbhdOut;
+int32_t pisces_hip_nbhd_default_criteria(PiscesNbhdCriteria* criteria);
+/* Over host arrays, no handle and no device: the statement of the contract and the function the device runs.  reference (optional):
+ * reference[i] is position i + 1; a neighbourhood's reference bytes are copied from first - 1 when the reference reaches
+ * last_with_look_ahead - 1, otherwise they are that many 'R' (CallableNeighborhood.cs:102-107).  PISCES_E_BUFFER_TOO_SMALL with the counts
+ * in n_out and nothing else written when a capacity is short; PISCES_E_INVALID_ARG / PISCES_E_UNSUPPORTED with n_out as above and a
+ * message; PISCES_E_INVALID_ARG for null criteria / rows / out / n_out, a negative row count or capacity, null recs with rows, a
+ * cand_index without cands and alleles, a null array with a capacity above 0, a negative reference length. */
+int32_t pisces_hip_nbhd_build(const PiscesNbhdCriteria* criteria, const PiscesVennRows* rows, const uint8_t* reference, int64_t reference_length,
+                              const PiscesNbhdOut* out);
+/* The same over device-resident rows, byte for byte, whichever wave runs first.  Asynchronous on `stream` (NULL: the handle's own),
+ * ordered behind whatever made the rows, no host wait inside: errors of the DATA (descending rows, a missing candidate, short capacities)
+ * arrive in n_out as above and the call still returns PISCES_OK.  Every call overwrites.  The reference bytes come from
+ * pisces_hip_set_reference's when it was called.  The scratch (about 50 bytes a row) is the handle's and only grows; calls of one handle
+ * must be stream-ordered with respect to each other, and a call that has to grow the scratch waits first. */
+int32_t pisces_hip_nbhd_build_device(PiscesHip* h, const PiscesNbhdCriteria* criteria, const PiscesVennRows* rows, const PiscesNbhdOut* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -209,6 +209,30 @@ VEAD_INFO_DTYPE = np.dtype([("first", "<i4"), ("last_with_look_ahead", "<i4"), (
                             ("n_groups", "<i4"), ("n_clipped_reads", "<i4"), ("n_reads_used", "<i4"), ("group_begin", "<i4")])
 
 
+# Scylla's neighbourhoods (pisces_hip_nbhd_*)
+class PiscesNbhdCriteria(C.Structure):
+    _fields_ = [("phasing_distance", C.c_int32), ("passing_variants_only", C.c_int32), ("het_variants_only", C.c_int32),
+                ("min_passing_variants_in_nbhd", C.c_int32), ("reserved", C.c_int32 * 4)]
+
+
+class PiscesNbhdInfo(C.Structure):
+    _fields_ = [("raw_index", C.c_int32), ("n_passing", C.c_int32), ("n_non_passing", C.c_int32), ("first", C.c_int32), ("last_in_vcf", C.c_int32),
+                ("last_with_look_ahead", C.c_int32), ("soft_clip_end_before", C.c_int32), ("soft_clip_pos_after", C.c_int32), ("ref_len", C.c_int32),
+                ("reserved", C.c_int32), ("ref_offset", C.c_int64)]
+
+
+class PiscesNbhdOut(C.Structure):
+    _fields_ = [("sites", C.c_void_p), ("alleles", C.c_void_p), ("site_row", C.c_void_p), ("site_original", C.c_void_p), ("neighbourhoods", C.c_void_p),
+                ("info", C.c_void_p), ("ref_bytes", C.c_void_p), ("row_class", C.c_void_p), ("n_out", C.c_void_p), ("nbhd_capacity", C.c_int64),
+                ("site_capacity", C.c_int64), ("allele_capacity", C.c_int64), ("ref_capacity", C.c_int64)]
+
+
+NBHD_ROW_FORCED, NBHD_ROW_INELIGIBLE, NBHD_ROW_LONE, NBHD_ROW_DROPPED, NBHD_ROW_KEPT = 0, 1, 2, 3, 4
+NBHD_INFO_DTYPE = np.dtype([("raw_index", "<i4"), ("n_passing", "<i4"), ("n_non_passing", "<i4"), ("first", "<i4"), ("last_in_vcf", "<i4"),
+                            ("last_with_look_ahead", "<i4"), ("soft_clip_end_before", "<i4"), ("soft_clip_pos_after", "<i4"), ("ref_len", "<i4"),
+                            ("reserved", "<i4"), ("ref_offset", "<i8")])
+
+
 # VariantComparisonCase (src/exe/VennVcf/VennVcf.cs:15-21) and the Venn classes of an input row (WriteVarsToVennFiles)
 VENN_AGREED_ON_REFERENCE, VENN_AGREED_ON_ALTERNATE, VENN_ONE_REFERENCE_ONE_ALTERNATE, VENN_CAN_NOT_COMBINE = 0, 1, 2, 3
 VENN_NONE, VENN_AND, VENN_NOT = 0, 1, 2

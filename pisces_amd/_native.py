@@ -34,6 +34,7 @@ EXPORTS = [
     "pisces_hip_vqr_default_options", "pisces_hip_vqr_count_device", "pisces_hip_vqr_count", "pisces_hip_vqr_tables", "pisces_hip_vqr_apply_device",
     "pisces_hip_venn_default_options", "pisces_hip_venn_consensus_device", "pisces_hip_venn_consensus", "pisces_hip_venn_combine",
     "pisces_hip_vead_default_options", "pisces_hip_vead_site_states", "pisces_hip_vead_neighborhood_info", "pisces_hip_vead_groups", "pisces_hip_vead_groups_device",
+    "pisces_hip_nbhd_default_criteria", "pisces_hip_nbhd_build", "pisces_hip_nbhd_build_device",
 ]
 
 
@@ -185,6 +186,9 @@ def _load():
         "pisces_hip_vead_neighborhood_info": (i32, [vp, i32, P(_abi.PiscesVeadNeighborhoodInfo)]),
         "pisces_hip_vead_groups": (i32, [P(_abi.PiscesVeadOptions), P(_abi.PiscesReadBatch), vp, i32, vp, i64, vp, i32, P(_abi.PiscesVeadOut)]),
         "pisces_hip_vead_groups_device": (i32, [vp, P(_abi.PiscesVeadOptions), P(_abi.PiscesReadBatch), i64, i64, vp, i32, vp, i64, vp, i32, P(_abi.PiscesVeadOut), vp]),
+        "pisces_hip_nbhd_default_criteria": (i32, [P(_abi.PiscesNbhdCriteria)]),
+        "pisces_hip_nbhd_build": (i32, [P(_abi.PiscesNbhdCriteria), P(_abi.PiscesVennRows), vp, i64, P(_abi.PiscesNbhdOut)]),
+        "pisces_hip_nbhd_build_device": (i32, [vp, P(_abi.PiscesNbhdCriteria), P(_abi.PiscesVennRows), P(_abi.PiscesNbhdOut), vp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(lib, name)   # AttributeError here = a declared symbol is not exported

@@ -11,7 +11,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libpisceship.so")
 SOURCES = ["pisces_hip.hip", "expander.cpp", "finder.cpp", "vcf_format.cpp", "diploid.cpp", "amplicon_bias.cpp", "exact_span.cpp", "indel_repeat.cpp"]
-HEADERS = ["kernels.hip.h", "stream_kernels.hip.h", "store_kernels.hip.h", "amplicon_kernels.hip.h", "exact_kernels.hip.h", "vcf_kernels.hip.h", "vcf_format.h", "exact_span.h", "indel_repeat.h", "indel_repeat_kernels.hip.h", "surface_amplicon.inc.h", "surface_exact.inc.h", "surface_indel_repeat.inc.h", "surface_vcf.inc.h", "vqr.h", "vqr_kernels.hip.h", "surface_vqr.inc.h", "venn.h", "venn_kernels.hip.h", "surface_venn.inc.h", "vead.h", "vead_kernels.hip.h", "surface_vead.inc.h", "surface_store.inc.h", "finder_kernels.hip.h", "bgzf_kernels.hip.h", "bam_kernels.hip.h", "bam_amplicon_kernels.hip.h", "device_math.hip.h", "surface_reads.inc.h", "surface_flush.inc.h", "surface_device.inc.h", "surface_bam.inc.h", "surface_comm.inc.h", "expander.h", "read_walk.h", "finder.h", "finder_walk.h", "diploid.h", "genotype_core.h", "amplicon_bias.h", "poisson_core.h", os.path.join("..", "..", "include", "pisces_hip.h")]
+HEADERS = ["kernels.hip.h", "stream_kernels.hip.h", "store_kernels.hip.h", "amplicon_kernels.hip.h", "exact_kernels.hip.h", "vcf_kernels.hip.h", "vcf_format.h", "exact_span.h", "indel_repeat.h", "indel_repeat_kernels.hip.h", "surface_amplicon.inc.h", "surface_exact.inc.h", "surface_indel_repeat.inc.h", "surface_vcf.inc.h", "vqr.h", "vqr_kernels.hip.h", "surface_vqr.inc.h", "venn.h", "venn_kernels.hip.h", "surface_venn.inc.h", "vead.h", "vead_kernels.hip.h", "surface_vead.inc.h", "nbhd.h", "nbhd_kernels.hip.h", "surface_nbhd.inc.h", "surface_store.inc.h", "finder_kernels.hip.h", "bgzf_kernels.hip.h", "bam_kernels.hip.h", "bam_amplicon_kernels.hip.h", "device_math.hip.h", "surface_reads.inc.h", "surface_flush.inc.h", "surface_device.inc.h", "surface_bam.inc.h", "surface_comm.inc.h", "expander.h", "read_walk.h", "finder.h", "finder_walk.h", "diploid.h", "genotype_core.h", "amplicon_bias.h", "poisson_core.h", os.path.join("..", "..", "include", "pisces_hip.h")]
 
 
 def hipcc_path():

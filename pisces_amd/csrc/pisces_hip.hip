@@ -45,6 +45,7 @@
 #include "vqr_kernels.hip.h"
 #include "venn_kernels.hip.h"
 #include "vead_kernels.hip.h"
+#include "nbhd_kernels.hip.h"
 #include "vcf_format.h"
 
 using namespace pisces;
@@ -654,6 +655,14 @@ public:
         DeviceBuf<unsigned long long> ctrl, keys;
         DeviceBuf<int64_t> prefix;
     } vead;
+    // pisces_hip_nbhd_build_device (nbhd_kernels.hip.h, Args): per-row, per-eligible-row and per-neighbourhood scratch, laid out for `rows` rows
+    struct NbhdScratch {
+        DeviceBuf<uint8_t> bytes;
+        DeviceBuf<int32_t> i32;
+        DeviceBuf<int64_t> i64;
+        DeviceBuf<unsigned long long> ctrl;
+        size_t rows = 0;
+    } nbhd;
 };
 
 #define PISCES_HIP_CHECK(h, expr)                                                              \
@@ -1265,6 +1274,7 @@ int32_t pisces_hip_set_owned_range(PiscesHip* h, int32_t lo, int32_t hi)
 
 #include "surface_venn.inc.h"
 #include "surface_vead.inc.h"
+#include "surface_nbhd.inc.h"
 
 int32_t pisces_hip_synchronize(PiscesHip* h)
 {

@@ -674,6 +674,59 @@ class HipVariantCaller:
                                                           site_rows.ctypes.data, len(site_rows), alleles.ctypes.data, alleles.size, nb.ctypes.data, len(nb),
                                                           C.byref(out), self._stream_arg(stream)))
 
+    def nbhd_build_device(self, rows, out, criteria=None, stream=None):
+        """pisces_hip_nbhd_build_device: Scylla's neighbourhoods from the device-resident rows of one chromosome (rows: venn_rows(...); out:
+        nbhd_out(...) over torch tensors, pinned host arrays or raw addresses, whose n_out is a device-accessible int64[6] that receives
+        kept neighbourhoods, sites, allele bytes, reference bytes, raw neighbourhoods and eligible rows — or an error word; nothing else
+        is written when a count is above its capacity).  Asynchronous on `stream` (None = the handle's own), no host wait inside."""
+        crit = criteria if criteria is not None else nbhd_criteria()
+        _check(self._h, lib.pisces_hip_nbhd_build_device(self._h, C.byref(crit), C.byref(rows), C.byref(out), self._stream_arg(stream)))
+
+    def phase_evidence_device(self, rows, batch=None, criteria=None, options=None, stream=None):
+        """What a Scylla host does with rows and reads that lie on the device: the neighbourhood tables of `rows` (venn_rows(...)) built
+        into pinned host arrays (counts first, then the sizes they ask for), one wait, then the tables handed to vead_groups_device over
+        `batch` (None: the batch bam_decode left on the device).  Returns {"nbhd": the tables as nbhd_build gives them, "groups", "states",
+        "info"}: the read pass's arrays.  An error word of the build raises PiscesHipError; the read pass's refusals (a neighbourhood above
+        VEAD_MAX_SITES among them) pass through unchanged."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        wait = (lambda: self.synchronize()) if stream is None else (lambda: torch.cuda.synchronize(dev))
+        pinned = lambda nbytes: torch.zeros(max(int(nbytes), 1), dtype=torch.uint8).pin_memory()
+        n = int(rows.n)
+        n_out = pinned(48)
+        caps = (0, 0, 0, 0)
+        while True:
+            t = {"sites": pinned(caps[1] * 16), "alleles": pinned(caps[2]), "site_row": pinned(caps[1] * 4), "site_original": pinned(caps[1] * 4),
+                 "neighbourhoods": pinned(caps[0] * 8), "info": pinned(caps[0] * 48), "ref_bytes": pinned(caps[3]), "row_class": pinned(n)}
+            out = nbhd_out(t["sites"], t["alleles"], t["site_row"], t["site_original"], t["neighbourhoods"], t["info"], t["ref_bytes"], n_out, *caps,
+                           row_class=t["row_class"])
+            self.nbhd_build_device(rows, out, criteria, stream)
+            wait()
+            counts = [int(v) for v in n_out.numpy()[:48].view(np.int64)]
+            if counts[0] < 0:
+                raise _nbhd_error_word(counts)
+            if all(c <= cap for c, cap in zip(counts[:4], caps)):
+                break
+            caps = tuple(counts[:4])
+        nbhd = _nbhd_result({k: v.numpy() for k, v in t.items()}, counts, n)
+        sites = (nbhd["sites"], nbhd["alleles"])
+        vead_n_out = pinned(24)
+        vcaps = (0, 0)
+        while True:
+            with torch.cuda.stream(self.torch_stream()):
+                groups = torch.zeros(max(vcaps[0], 1) * 24, dtype=torch.uint8, device=dev)
+                states = torch.zeros(max(vcaps[1], 1), dtype=torch.uint8, device=dev)
+                info = torch.zeros(max(counts[0], 1) * 32, dtype=torch.uint8, device=dev)
+            self.synchronize()
+            self.vead_groups_device(sites, nbhd["neighbourhoods"], vead_out(groups, states, info, vead_n_out, *vcaps), batch=batch, options=options, stream=stream)
+            wait()
+            got = [int(v) for v in vead_n_out.numpy()[:24].view(np.int64)]
+            if got[0] <= vcaps[0] and got[1] <= vcaps[1]:
+                break
+            vcaps = (got[0], got[1])
+        return {"nbhd": nbhd, "groups": groups.cpu().numpy()[:got[0] * 24].view(_abi.VEAD_GROUP_DTYPE).copy(), "states": states.cpu().numpy()[:got[1]].copy(),
+                "info": info.cpu().numpy()[:counts[0] * 32].view(_abi.VEAD_INFO_DTYPE).copy()}
+
     def accumulate_tiles(self, d_tuples, d_tiles, n_tiles, d_counts, stream=None):
         _check(self._h, lib.pisces_hip_accumulate_tiles(self._h, d_tuples, d_tiles, n_tiles, d_counts, self._stream_arg(stream)))
 
@@ -1357,3 +1410,85 @@ def vead_groups(batch, sites, neighborhoods, options=None, capacities=None):
             err.n_out = tuple(int(v) for v in n_out)
             raise err
         return {"groups": groups[:int(n_out[0])], "states": states[:int(n_out[1])], "info": info[:len(nb)], "n_out": tuple(int(v) for v in n_out)}
+
+
+# ---- Scylla's neighbourhoods (pisces_hip_nbhd_*) ----------------------------------------------------------------------------------------
+def nbhd_criteria(**overrides):
+    """PiscesNbhdCriteria with Scylla's defaults (pisces_hip_nbhd_default_criteria), fields overridden by name."""
+    crit = _abi.PiscesNbhdCriteria()
+    _check(None, lib.pisces_hip_nbhd_default_criteria(C.byref(crit)))
+    for k, v in overrides.items():
+        if not hasattr(crit, k):
+            raise AttributeError(f"PiscesNbhdCriteria has no field {k!r}")
+        setattr(crit, k, int(v))
+    return crit
+
+
+def nbhd_out(sites, alleles, site_row, site_original, neighbourhoods, info, ref_bytes, n_out, nbhd_capacity, site_capacity, allele_capacity, ref_capacity,
+             row_class=None):
+    """PiscesNbhdOut: where the tables go (torch tensors, numpy arrays, ctypes arrays or raw addresses; the caller keeps them alive)."""
+    o = _abi.PiscesNbhdOut()
+    o.sites, o.alleles, o.site_row, o.site_original = _address(sites), _address(alleles), _address(site_row), _address(site_original)
+    o.neighbourhoods, o.info, o.ref_bytes, o.row_class, o.n_out = _address(neighbourhoods), _address(info), _address(ref_bytes), _address(row_class), _address(n_out)
+    o.nbhd_capacity, o.site_capacity, o.allele_capacity, o.ref_capacity = int(nbhd_capacity), int(site_capacity), int(allele_capacity), int(ref_capacity)
+    return o
+
+
+def _nbhd_error_word(counts):
+    """the PiscesHipError of an n_out that holds an error word"""
+    if counts[0] == _abi.E_INVALID_ARG and counts[1] == 0:
+        text = f"nbhd_build_device: the rows are not sorted by position at row {counts[2]}"
+    elif counts[0] == _abi.E_INVALID_ARG:
+        text = f"nbhd_build_device: row {counts[2]} is an insertion, deletion or MNV without a candidate to take its alleles from"
+    else:
+        text = "nbhd_build_device: more than 2^31 - 1 allele or reference bytes"
+    err = PiscesHipError(counts[0], text)
+    err.n_out = tuple(counts)
+    return err
+
+
+def _nbhd_result(raw, counts, n_rows):
+    """the tables cut to their counts, from byte (or typed) arrays"""
+    k, ns, nb, nr = counts[:4]
+    as_bytes = lambda a: np.ascontiguousarray(a).view(np.uint8).reshape(-1)
+    return {"sites": as_bytes(raw["sites"])[:ns * 16].view(_abi.VEAD_SITE_DTYPE).copy(), "alleles": as_bytes(raw["alleles"])[:nb].copy(),
+            "site_row": as_bytes(raw["site_row"])[:ns * 4].view(np.int32).copy(), "site_original": as_bytes(raw["site_original"])[:ns * 4].view(np.int32).copy(),
+            "neighbourhoods": as_bytes(raw["neighbourhoods"])[:k * 8].view(_abi.VEAD_NEIGHBORHOOD_DTYPE).copy(),
+            "info": as_bytes(raw["info"])[:k * 48].view(_abi.NBHD_INFO_DTYPE).copy(), "ref_bytes": as_bytes(raw["ref_bytes"])[:nr].copy(),
+            "row_class": as_bytes(raw["row_class"])[:n_rows].copy(), "n_out": tuple(counts)}
+
+
+def nbhd_build(records, alleles=None, criteria=None, reference=None, capacities=None, count=None):
+    """pisces_hip_nbhd_build: Scylla's neighbourhoods over host rows (a CALLED_ALLELE_DTYPE array of one chromosome, sorted by position);
+    alleles: format_vcf's (ref, alt) pairs when there are insertion / deletion / MNV rows; reference: the chromosome's bases (position p at
+    [p - 1]) or None; count: a row count below len(records).  Returns {sites (VEAD_SITE_DTYPE), alleles, site_row, site_original,
+    neighbourhoods (VEAD_NEIGHBORHOOD_DTYPE), info (NBHD_INFO_DTYPE), ref_bytes, row_class, n_out}.  capacities: (neighbourhoods, sites,
+    allele bytes, reference bytes) to offer; by default the call is repeated with the sizes it reports.  A refusal raises PiscesHipError
+    whose n_out attribute holds the six words."""
+    crit = criteria if criteria is not None else nbhd_criteria()
+    recs = np.ascontiguousarray(records, dtype=_abi.CALLED_ALLELE_DTYPE)
+    table = candidate_table(recs, alleles) if alleles is not None else (None, None, None)
+    count_word = None if count is None else np.array([count], dtype=np.int32)
+    rows = venn_rows(recs if len(recs) else None, len(recs), count_word, *table)
+    if reference is not None:
+        reference = np.frombuffer(reference.encode() if isinstance(reference, str) else bytes(reference), dtype=np.uint8) if not isinstance(reference, np.ndarray) \
+            else np.ascontiguousarray(reference, np.uint8)
+    caps = tuple(capacities) if capacities is not None else (0, 0, 0, 0)
+    while True:
+        raw = {"sites": np.zeros(max(caps[1], 1), dtype=_abi.VEAD_SITE_DTYPE), "alleles": np.zeros(max(caps[2], 1), np.uint8),
+               "site_row": np.zeros(max(caps[1], 1), np.int32), "site_original": np.zeros(max(caps[1], 1), np.int32),
+               "neighbourhoods": np.zeros(max(caps[0], 1), dtype=_abi.VEAD_NEIGHBORHOOD_DTYPE), "info": np.zeros(max(caps[0], 1), dtype=_abi.NBHD_INFO_DTYPE),
+               "ref_bytes": np.zeros(max(caps[3], 1), np.uint8), "row_class": np.full(max(len(recs), 1), 255, np.uint8)}
+        n_out = np.zeros(6, dtype=np.int64)
+        out = nbhd_out(raw["sites"], raw["alleles"], raw["site_row"], raw["site_original"], raw["neighbourhoods"], raw["info"], raw["ref_bytes"], n_out, *caps,
+                       row_class=raw["row_class"])
+        rc = lib.pisces_hip_nbhd_build(C.byref(crit), C.byref(rows), None if reference is None else reference.ctypes.data,
+                                       0 if reference is None else reference.size, C.byref(out))
+        if rc == _abi.E_BUFFER_TOO_SMALL and capacities is None:
+            caps = tuple(int(v) for v in n_out[:4])
+            continue
+        if rc != 0:
+            err = PiscesHipError(rc, (lib.pisces_hip_last_error(None) or b"").decode())
+            err.n_out = tuple(int(v) for v in n_out)
+            raise err
+        return _nbhd_result(raw, [int(v) for v in n_out], len(recs) if count is None else max(0, min(len(recs), int(count))))
